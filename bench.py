@@ -1,7 +1,14 @@
 """Benchmark: NeuS volume rendering, 4096 rays x 128 samples, 8x256 SDF MLP (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (same layout)
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step; the dominant kernel's roofline from the HIP events of the timed steps).  Everything
+else below (the every-mid-point loop, the per-kernel census, the config-(d) frame, the scaling legs,
+the fp32 mode, configs (c)/(e)/training, the CPU and eager-GPU baselines) takes runs of its own and
+is measured only under --full, where each part can still be switched off by its --no-* option.
 
 A step = one `volume_render` call (render mode: torch.no_grad, perturb=False, calc_normal=True,
 detailed_output=False) over one 4096-ray batch of the synthetic config-(b) camera (64x64 pixels,
@@ -110,8 +117,17 @@ def parse():
     ap.add_argument('--leg-steps', type=int, default=5)
     ap.add_argument('--no-fp32-mode', action='store_true',
                     help='skip the exact-fp32 rate of config (b) beside the f16x3 headline')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline figure (every part below that its --no-* '
+                         'option does not switch off); a plain run times the K steps and nothing else')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32/float64; rank r > 0 "
+                         "writes <name>.rank<r>.npy), at most 64 MB in all: larger outputs as a fixed seeded sample")
     ap.add_argument('--stub-cpu', action='store_true', help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def make_model(device, precision, outside=False):
@@ -484,6 +500,8 @@ def train_setup(dev, precision, n_rays, world, adam='nr', nerfpp=False):
         opt.zero_grad()
         ret['losses']['total'].backward()
         opt.step()
+        return ret['losses']
+    step.model = model   # --dump-outputs writes the parameters after the last timed step beside its losses
     return step
 
 
@@ -773,19 +791,71 @@ def launch(args):
                        start_method='spawn')
 
 
-def timed(step, steps, warmup, sync, barrier):
-    """W untimed steps, then K steps bracketed by barrier + device sync on both sides"""
+def timed(step, steps, warmup, sync, barrier, keep=None):
+    """W untimed steps, then K steps bracketed by barrier + device sync on both sides; what the last
+    timed step returned is appended to `keep` (a list) when one is given"""
     for _ in range(warmup):
         step()
     sync()
     barrier()
     sync()
+    out = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     sync()
     barrier()
-    return time.perf_counter() - t0
+    dt = time.perf_counter() - t0
+    if keep is not None:
+        keep.append(out)
+    return dt
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def _named_arrays(obj, prefix=''):
+    """flatten a step's return value (tensor, or tuples / dicts of them) into (name, tensor) pairs;
+    a tensor reachable under several names (rgb is also extras['rgb']) is listed once"""
+    out, seen = [], set()
+
+    def walk(o, name):
+        if isinstance(o, torch.Tensor):
+            if id(o) not in seen:
+                seen.add(id(o))
+                out.append((name or 'out', o))
+        elif isinstance(o, dict):
+            for k, v in o.items():
+                walk(v, f'{name}.{k}' if name else str(k))
+        elif isinstance(o, (tuple, list)):
+            # a render returns (rgb, depth, extras) with both maps in extras too: the dict's names win
+            for v in o:
+                if isinstance(v, dict):
+                    walk(v, name)
+            for i, v in enumerate(o):
+                if not isinstance(v, dict):
+                    walk(v, f'{name}.{i}' if name else f'out{i}')
+    walk(obj, prefix)
+    return out
+
+
+def dump_outputs(path, result, rank=0):
+    """--dump-outputs: every array of `result` as path/<name>.npy (float64 stays float64, everything else
+    float32).  Outputs over DUMP_MAX_BYTES in all are cut to a fixed sample each: the flat elements at
+    indices drawn once by numpy's RandomState(0), sorted, the same for every run and build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = []
+    for name, t in _named_arrays(result):
+        a = t.detach().cpu().numpy()
+        arrs.append((name, a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)))
+    total = sum(a.nbytes for _, a in arrs)
+    for name, a in arrs:
+        if total > DUMP_MAX_BYTES:
+            keep_n = max(1, int(a.size * (DUMP_MAX_BYTES / total) * 0.99))
+            idx = np.sort(np.random.RandomState(0).choice(a.size, keep_n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ('' if rank == 0 else f'.rank{rank}') + '.npy'), a)
 
 
 def main():
@@ -856,20 +926,23 @@ def run(args):
     # library kernels' times (the per-kernel table, the dominant kernel's share, executed FLOPs of the
     # whole step) come from a census of a few more steps with every launch recorded, after the timing.
     dom_prefix = 'train_gemm' if args.workload == 'train' else 'sdf_nabla'
+    last = []                      # what the last timed step of the headline loop returned
 
-    def profiled(fn):
-        """(max-over-ranks time of the timed steps, dominant-kernel stats of the timed steps, every
-        library kernel's stats of a census pass scaled to the timed step count)"""
+    def profiled(fn, keep=None):
+        """(max-over-ranks time of the timed steps, dominant-kernel stats of the timed steps, and under
+        --full every library kernel's stats of a census pass scaled to the timed step count, else None)"""
         for _ in range(args.warmup):
             fn()
         sync()
         L.profile_read()           # drop warm-up records
         L.profile_enable(True, dom_prefix)
         try:
-            dt = timed(fn, args.steps, 0, sync, barrier)
+            dt = timed(fn, args.steps, 0, sync, barrier, keep)
         finally:
             L.profile_enable(False)
         kdom = L.profile_read()
+        if not args.full:
+            return max_over_ranks(dt), kdom, None
         n_census = min(3, args.steps)
         L.profile_enable(True)
         try:
@@ -882,12 +955,20 @@ def run(args):
         census = {k: (round(n * f), ms * f, u * f) for k, (n, ms, u) in L.profile_read().items()}
         return max_over_ranks(dt), kdom, census
 
-    dt, kstats, census = profiled(step)
+    dt, kstats, census = profiled(step, last)
+    if args.dump_outputs:
+        result = last[0]
+        if args.workload == 'train':
+            result = {'losses': result, 'params': dict(step.model.named_parameters())}
+        dump_outputs(args.dump_outputs, result, rank)
+    del last[:]
+    # everything from here to the result line takes runs of its own: --full only
+    extras = args.full and args.workload == 'b'
     full = None
-    if args.workload not in ('frame_d', 'train') and not args.no_full_eval:  # every mid-point evaluated
+    if extras and not args.no_full_eval:  # every mid-point evaluated
         full = profiled(step_full)
     frame = None
-    if args.workload == 'b' and not args.no_frame:
+    if extras and not args.no_frame:
         # strong scaling: one config-(d) 800x600 frame per step split over all ranks, all_gather timed
         fstep, frame_rays = frame_d_setup(dev, args.precision, args.frame_workspace_gb)
         fdt = max_over_ranks(timed(fstep, args.frame_steps, 1, sync, barrier))
@@ -898,13 +979,13 @@ def run(args):
                  'scaling': 'strong', 'rays_per_step': frame_rays, 'rays_per_gpu': frame_rays // world,
                  'parallelism': f'ray-sharded x{world} + all_gather'}
     legs = None
-    if args.workload == 'b' and not args.no_scaling_legs:
+    if extras and not args.no_scaling_legs:
         legs = scaling_legs(args, dev, world, sync, barrier, max_over_ranks)
     f32 = None
-    if args.workload == 'b' and args.precision == 'f16x3' and not args.no_fp32_mode and world == 1:
+    if extras and args.precision == 'f16x3' and not args.no_fp32_mode and world == 1:
         f32 = fp32_mode(args, dev, sync)
     cfgs = None
-    if args.workload == 'b' and not args.no_configs and world == 1:
+    if extras and not args.no_configs and world == 1:
         cs, cw = args.config_steps, 1
         cfgs = {'c_volsdf_2048x256': config_c(dev, args.precision, cs, cw, sync),
                 'e_unisurf_4096': config_e(dev, args.precision, cs, cw, sync),
@@ -956,10 +1037,11 @@ def run(args):
                            'rays_per_gpu': n_rays // world, 'samples_per_ray': 128, 'precision': args.precision,
                            'parallelism': f'ray-sharded x{world}'},
                 'roofline': roof,
-                # executed MLP FLOPs (fp32-equivalent) per second over the whole step
-                'step_tflops': round(executed_flop(census) / args.steps / (dt / args.steps) / 1e12, 2),
                 'mid_points_evaluated_frac': mid_frac(kstats, n_rays // world, args.steps),
             }
+            if census is not None:
+                # executed MLP FLOPs (fp32-equivalent) per second over the whole step
+                out['step_tflops'] = round(executed_flop(census) / args.steps / (dt / args.steps) / 1e12, 2)
             if full is not None:
                 dtf, kf, kfc = full
                 out['full_evaluation'] = {
@@ -979,14 +1061,14 @@ def run(args):
             out['config']['zero_alpha_skip'] = ('mid-points whose alpha is exactly 0 (no SDF decrease between the '
                                                 'two samples, neus.py:28-35) get weight 0 and skip the nets; '
                                                 'rgb/depth/mask/normals bit-identical to full evaluation')
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 out['cpu_baseline'] = cpu_baseline(args.cpu_rays)
                 eg = eager_gpu_baseline(dev, n_rays)
                 eg['speedup'] = round(value / eg['value'], 2)
                 out['cpu_baseline']['eager_gpu_reference'] = eg
         out['config']['build_id'] = L.build_id()  # source hash compiled into libnrhip.so (neurecon_amd/build.py)
         out['config']['workspace_gb'] = args.workspace_gb if args.workspace_gb is not None else 'library default (4 GiB)'
-        if args.workload == 'b' and not args.no_frame:
+        if frame is not None:
             out['strong_scaling_frame_d']['workspace_gb'] = args.frame_workspace_gb
         print(json.dumps(out), flush=True)
     if dist:
@@ -1003,6 +1085,7 @@ def run_stub(args, world, rank):
         world = tdist.get_world_size()
     if args.gpus is not None and args.gpus != world:
         raise SystemExit(f'bench: --gpus {args.gpus} but the process group has {world} ranks')
+    torch.manual_seed(0)
     a = torch.randn(64, 64)
     barrier = tdist.barrier if dist else (lambda: None)
 
@@ -1012,7 +1095,10 @@ def run_stub(args, world, rank):
         t = torch.tensor([x])
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         return float(t.item())
-    dt = max_over_ranks(timed(lambda: a @ a, args.steps, args.warmup, lambda: None, barrier))
+    last = []
+    dt = max_over_ranks(timed(lambda: a @ a, args.steps, args.warmup, lambda: None, barrier, last))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], rank)
     ranks = [rank]
     if dist:
         got = [None] * world
@@ -1021,11 +1107,17 @@ def run_stub(args, world, rank):
     out = {'metric': 'stub', 'value': args.steps * world / dt, 'unit': 'steps/s', 'n_gpus': world,
            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
            'ranks': ranks, 'pid': os.getpid()}
-    if not args.no_scaling_legs:
+    if args.full and not args.no_scaling_legs:
         out.update(stub_legs(args, world, barrier, max_over_ranks))
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist:
+        # a rank that tore its gloo sockets down while the other still used them made that one abort
+        # now and then ("terminate called without an active exception"): leave together, and let the
+        # legs' DDP reducer go before its process group
+        import gc
+        gc.collect()
+        tdist.barrier()
         tdist.destroy_process_group()
 
 

@@ -23,10 +23,10 @@ def _run(cmd):
 
 
 def test_bench_spawns_n_ranks():
-    out = _run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--stub-cpu'])
+    out = _run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--stub-cpu', '--full'])
     assert out['n_gpus'] == 2 and sorted(out['ranks']) == [0, 1]
     assert out['steps'] == 2 and out['warmup'] == 1
-    # the weak-scaling legs of the default N-GPU line: config (e)'s sharded render with its window
+    # the weak-scaling legs of the N-GPU line under --full: config (e)'s sharded render with its window
     # all-reduce in the step, and the DDP training step
     for leg in ('weak_scaling_e', 'weak_scaling_train'):
         assert out[leg]['n_gpus'] == 2 and out[leg]['scaling'] == 'weak' and out[leg]['value'] > 0, out[leg]
@@ -34,9 +34,27 @@ def test_bench_spawns_n_ranks():
 
 
 def test_bench_single_process_default():
-    out = _run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--stub-cpu'])
+    out = _run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--stub-cpu', '--full'])
     assert out['n_gpus'] == 1 and out['ranks'] == [0]
     assert out['weak_scaling_e']['n_gpus'] == 1 and not out['weak_scaling_e']['collective_in_step']
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """without --full: the timed steps and the result line only (no scaling legs), --steps sets the
+    number of timed steps, and --dump-outputs writes the last step's result, the same from run to run"""
+    import numpy as np
+    outs = []
+    for d in ('a', 'b'):
+        out = _run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--stub-cpu',
+                    '--dump-outputs', str(tmp_path / d)])
+        assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0
+        assert abs(out['value'] - 1e3 / out['ms_per_step']) <= 1e-6 * out['value']   # steps/s of the 3 steps
+        assert 'weak_scaling_e' not in out and 'weak_scaling_train' not in out
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ['out.npy'], files
+        outs.append(np.load(tmp_path / d / 'out.npy'))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (64, 64)
+    assert np.array_equal(outs[0], outs[1])
 
 
 def _free_port():

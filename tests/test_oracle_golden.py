@@ -3,6 +3,8 @@
 CPU-only.  The oracle runs the same fp32 torch CPU kernels as the reference, so agreement is at
 rounding level; tolerances below are written per quantity.
 """
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -14,6 +16,32 @@ from oracle.volsdf import VolSDFOracle, error_bound, sdf_to_sigma
 from oracle.unisurf import UNISURFOracle
 
 T = lambda a: torch.from_numpy(np.asarray(a))
+
+# The bars below hold only against the reference run on the same torch fp32 CPU kernels as the oracle,
+# and those differ from host to host: MKL picks its sgemm by the CPU it finds, and on some hosts the
+# reference itself does not reproduce tests/golden/*.npz to rounding (sdf_net differs in the last bits,
+# neus_b by up to 0.16 once a rounding flips one of the sampler's discrete choices).  So the reference's
+# vectors are kept from two runs of the same gen_golden.py: tests/golden/ (which the GPU tests' bars were
+# measured against, and keep) and, where a file differs, tests/golden/oracle_pin/ from a host of the
+# other kind.  This module checks the oracle against the run whose kernels this host shares, told by
+# which run's SDF forward pass the host's own is nearer to; every bar is the same for either run.
+PIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'oracle_pin')
+
+
+@pytest.fixture(scope='module')
+def golden(golden):
+    first = golden
+
+    def second(name):
+        p = os.path.join(PIN, name + '.npz')
+        return dict(np.load(p)) if os.path.exists(p) else first(name)
+    g = first('sdf_net')
+    with torch.no_grad():
+        s, _ = nets.SDFNet(wg.neus_state(seed=int(g['seed']))).forward(T(g['pts']))
+    err = [float(np.abs(s.numpy() - run('sdf_net')['sdf_nograd']).max()) for run in (first, second)]
+    print(f'reference run with this host\'s kernels: {"golden/" if err[0] <= err[1] else "golden/oracle_pin/"} '
+          f'(SDF forward max abs difference {err[0]:.2e} / {err[1]:.2e})')
+    return first if err[0] <= err[1] else second
 
 
 def close(a, b, rtol=1e-5, atol=1e-6):

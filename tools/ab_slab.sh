@@ -6,7 +6,7 @@ mkdir -p gpurun_out/ab
 for r in 1 2 3; do
   for v in A B; do
     if [ $v = A ]; then lib=neurecon_amd/_exp/abA.so; else lib=neurecon_amd/libnrhip.so; fi
-    NR_LIB=$lib timeout -k 10 150 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-frame --no-configs \
+    NR_LIB=$lib timeout -k 10 150 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-frame --no-configs \
       --workspace-gb 8 "$@" > gpurun_out/ab/slab_$v$r.log 2>&1 || exit $?
     echo "$v$r $(grep -o '"value": [0-9.]*' gpurun_out/ab/slab_$v$r.log | head -1) $(grep -o '"frac": [0-9.]*' gpurun_out/ab/slab_$v$r.log | head -1)"
   done

@@ -11,7 +11,7 @@ if [ -n "$TESTS" ]; then
   timeout -k 10 ${T_TEST:-400} python3 -u -m pytest -x -q --timeout 120 --timeout-method thread -m gpu $TESTS > $O/pytest.log 2>&1
   rc=$?; tail -n 3 $O/pytest.log; [ $rc -eq 0 ] || { echo "tests failed rc=$rc"; exit 1; }
 fi
-B="python3 bench.py --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-frame --no-configs ${BENCH_ARGS:---no-full-eval}"
+B="python3 bench.py --full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-frame --no-configs ${BENCH_ARGS:---no-full-eval}"
 for r in $(seq ${ROUNDS:-2}); do
   for lib in default $VARIANTS; do
     tag=$(basename $lib .so)

@@ -16,17 +16,17 @@ if [ -z "$NO_TESTS" ]; then
   tail -n 1 $O/pytest_gpu.txt
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -n 20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -n 20 $O/bench.err; exit 1; }
   tail -c 400 $O/bench.json
 fi
 if [ -n "$PROFILES" ]; then
   TAG=${TAG}_m STEPS=20 bash tools/gpu_mfma_r05.sh > $O/mfma.log 2>&1 || { echo "mfma passes failed"; tail -n 5 $O/mfma.log; exit 1; }
-  B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-frame --no-configs --no-scaling-legs --no-fp32-mode"
+  B="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-frame --no-configs --no-scaling-legs --no-fp32-mode"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/b_full -o run -- $B > $O/b_full.log 2>&1 || { echo "b_full prof failed"; exit 1; }
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -o run -- python3 bench.py --workload train --steps 5 --warmup 2 > $O/train.log 2>&1 || { echo "train prof failed"; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -o run -- python3 bench.py --full --workload train --steps 5 --warmup 2 > $O/train.log 2>&1 || { echo "train prof failed"; exit 1; }
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_b/$C -o run -- $B --steps 3 --warmup 1 --no-full-eval > $O/pmc_b_$C.log 2>&1 || { echo "pmc b $C failed"; exit 1; }
-    timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_train/$C -o run -- python3 bench.py --workload train --steps 3 --warmup 1 > $O/pmc_train_$C.log 2>&1 || { echo "pmc train $C failed"; exit 1; }
+    timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_train/$C -o run -- python3 bench.py --full --workload train --steps 3 --warmup 1 > $O/pmc_train_$C.log 2>&1 || { echo "pmc train $C failed"; exit 1; }
   done
   python3 tools/pmc_summary.py $O/pmc_b > $O/f16x3_pmc_summary.json && python3 tools/pmc_summary.py $O/pmc_train > $O/train_pmc_summary.json && echo "profiles ok"
 fi

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 O=gpurun_out/${TAG:-r05m}
 mkdir -p $O
-B="python3 bench.py --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-frame --no-configs --no-full-eval ${BENCH_ARGS}"
+B="python3 bench.py --full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-frame --no-configs --no-full-eval ${BENCH_ARGS}"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B > $O/stats.log 2>&1 \
   || { echo "stats pass failed"; tail -5 $O/stats.log; exit 1; }
 tail -1 $O/stats.log | cut -c1-400

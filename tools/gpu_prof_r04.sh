@@ -23,14 +23,14 @@ pmc() {  # tag, counter, command...
   timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$tag/$c -o run -- "$@" > $O/pmc_$tag/$c.log 2>&1
   local rc=$?; echo "pmc $tag $c rc=$rc"; return $rc
 }
-B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-frame --no-configs"
+B="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-frame --no-configs"
 run b 300 $B --no-full-eval &&
 run b_full 300 $B &&
-run train 300 python3 bench.py --workload train --steps 5 --warmup 2 &&
-run frame_d 400 python3 bench.py --workload frame_d --steps 2 --warmup 1 &&
+run train 300 python3 bench.py --full --workload train --steps 5 --warmup 2 &&
+run frame_d 400 python3 bench.py --full --workload frame_d --steps 2 --warmup 1 &&
 pmc b FETCH_SIZE $B --steps 3 --warmup 1 --no-full-eval &&
 pmc b WRITE_SIZE $B --steps 3 --warmup 1 --no-full-eval &&
-pmc train FETCH_SIZE python3 bench.py --workload train --steps 3 --warmup 1 &&
-pmc train WRITE_SIZE python3 bench.py --workload train --steps 3 --warmup 1 &&
+pmc train FETCH_SIZE python3 bench.py --full --workload train --steps 3 --warmup 1 &&
+pmc train WRITE_SIZE python3 bench.py --full --workload train --steps 3 --warmup 1 &&
 python3 tools/pmc_summary.py $O/pmc_b > $O/f16x3_pmc_summary.json &&
 python3 tools/pmc_summary.py $O/pmc_train > $O/train_pmc_summary.json && echo pmc ok

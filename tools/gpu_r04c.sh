@@ -15,6 +15,6 @@ rc=$?; echo "wgrad tests rc=$rc"; grep -E "max \||nr_wgrad" $O/pytest_wgrad.log 
 timeout -k 10 ${T_TEST:-900} python3 -u -m pytest tests -m gpu -v -rA -s --timeout 300 --timeout-method thread ${PYTEST_ARGS} > $O/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed" $O/pytest_gpu.log | tail -8
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 600 python3 -u bench.py > $O/bench.log 2>&1
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.log 2>&1
 rb=$?; echo "bench rc=$rb"; tail -1 $O/bench.log | cut -c1-700
 exit $rc

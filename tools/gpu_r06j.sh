@@ -22,6 +22,6 @@ PY
 done
 [ -n "$NO_TRAIN" ] && exit 0
 for extra in "" "--train-nerfpp"; do
-  timeout -k 10 400 python3 bench.py --workload train $extra --steps 20 --warmup 3 > $O/train$extra.json 2> $O/train$extra.err || { echo "train bench failed"; tail -5 $O/train$extra.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --workload train $extra --steps 20 --warmup 3 > $O/train$extra.json 2> $O/train$extra.err || { echo "train bench failed"; tail -5 $O/train$extra.err; exit 1; }
   python3 -c "import json,sys; d=json.loads(open('$O/train$extra.json').read().strip().splitlines()[-1]); print('train$extra', round(d['value']), d['unit'], d['ms_per_step'])"
 done

@@ -14,7 +14,7 @@ tail -n 1 $O/pytest_more.txt
 for r in 1 2 3; do
   for L in neurecon_amd/libnrhip.so $ALT; do
     b=$(basename $L .so)
-    NR_LIB=$PWD/$L timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-frame --no-configs --no-scaling-legs --no-fp32-mode > $O/b_${r}_$b.json 2> $O/b_${r}_$b.err || { echo "bench failed"; tail -5 $O/b_${r}_$b.err; exit 1; }
+    NR_LIB=$PWD/$L timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-frame --no-configs --no-scaling-legs --no-fp32-mode > $O/b_${r}_$b.json 2> $O/b_${r}_$b.err || { echo "bench failed"; tail -5 $O/b_${r}_$b.err; exit 1; }
     echo "b $b: $(python3 -c 'import json,sys; d=json.load(open(sys.argv[1])); r=d["roofline"]; print(d["value"], d["ms_per_step"], {k: v["avg_launch_ms"] for k, v in r["per_launch_type"].items()}, d["full_evaluation"]["value"] if "full_evaluation" in d else "")' $O/b_${r}_$b.json)"
   done
 done

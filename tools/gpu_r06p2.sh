@@ -11,7 +11,7 @@ tail -n 1 $O/pytest.txt
 for r in 1 2 3; do
   for L in neurecon_amd/libnrhip.so $ALT; do
     b=$(basename $L .so)
-    NR_LIB=$PWD/$L timeout -k 10 300 python3 bench.py --workload train --steps 20 --warmup 3 > $O/t_${r}_$b.json 2> $O/t_${r}_$b.err || { echo "bench train failed"; tail -5 $O/t_${r}_$b.err; exit 1; }
+    NR_LIB=$PWD/$L timeout -k 10 300 python3 bench.py --full --workload train --steps 20 --warmup 3 > $O/t_${r}_$b.json 2> $O/t_${r}_$b.err || { echo "bench train failed"; tail -5 $O/t_${r}_$b.err; exit 1; }
     echo "train $b: $(python3 -c 'import json,sys; d=json.load(open(sys.argv[1])); print(d["value"], d["ms_per_step"])' $O/t_${r}_$b.json)"
   done
 done

@@ -16,6 +16,6 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
 fi
 [ -n "$SKIP_BENCH" ] && exit 0
-timeout -k 10 ${T_BENCH:-600} python3 -u bench.py ${BENCH_ARGS} > $O/bench.log 2>&1
+timeout -k 10 ${T_BENCH:-600} python3 -u bench.py --full ${BENCH_ARGS} > $O/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -1 $O/bench.log | cut -c1-600
 exit $rc

@@ -9,6 +9,6 @@ if [ -n "$TESTS" ]; then
   rc=$?; tail -n 3 $O/pytest.log; [ $rc -eq 0 ] || { echo "tests failed rc=$rc"; grep -E "FAILED|Error" $O/pytest.log | head -20; exit 1; }
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 ${T_BENCH:-400} python3 bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -n 20 $O/bench.err; exit 1; }
+  timeout -k 10 ${T_BENCH:-400} python3 bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -n 20 $O/bench.err; exit 1; }
   tail -c 3000 $O/bench.json
 fi

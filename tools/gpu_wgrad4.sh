@@ -11,6 +11,6 @@ timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pro
 grep "nr_wgrad\|hipBLAS" $O/prof.log
 timeout -k 10 400 python3 -u -m pytest tests/test_gpu_raybatch.py -v -rA -s --timeout 300 --timeout-method thread -k random_batch > $O/pytest.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed|batch, worst|weight_v" $O/pytest.log | tail -14; [ $rc = 0 ] || exit $rc
-timeout -k 10 600 python3 -u bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.log 2>&1 || exit $?
 tail -c 3000 $O/bench.log
 bash tools/ab_slab.sh

@@ -11,6 +11,6 @@ for v in base wg_nomfma wg_nostore wg_loadonly wg_noload; do
 done
 timeout -k 10 400 python3 -u -m pytest tests/test_gpu_raybatch.py -v -rA -s --timeout 300 --timeout-method thread -k random_batch > $O/pytest.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "^FAILED|passed|failed|batch, worst" $O/pytest.log | tail -6; [ $rc = 0 ] || exit $rc
-timeout -k 10 600 python3 -u bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.log 2>&1 || exit $?
 tail -c 2500 $O/bench.log
 bash tools/ab_slab.sh
