@@ -632,7 +632,9 @@ int nr_unisurf_composite_bwd(const float* logits, const float* rad, const float*
  * transposed ops) and the training pack (nr_sdf_train_pack: W8^T with W8[0, :] as its row vector;
  * nr_radiance_train_pack: the radiance net's transposed ops); nr_*_op_info give an op's byte offset
  * in its buffer, input blocks and output blocks.  Supported (KB, KB2, NBO, NB2, mode) shapes are the
- * training path's own (NR_ERR_UNSUPPORTED otherwise).
+ * training path's own (NR_ERR_UNSUPPORTED otherwise).  The kernel addresses every tensor by 32-bit byte
+ * offsets: P * ld * 4 must stay below 2 GB for the inputs (ld1, ld2), the outputs and the epilogue
+ * tensors alike (NR_ERR_ARG otherwise, before any launch).
  * ------------------------------------------------------------------------------------------ */
 #define NR_TG_NONE 0
 #define NR_TG_SOFTPLUS 1

@@ -3566,14 +3566,26 @@ int launch_tgemm(const TGemmArgs& a, int KB, int KB2, int NBO, int NB2, hipStrea
   if (a.P <= 0) return NR_OK;
   NR_REQUIRE(a.op && (a.y || a.yb || a.y2 || a.y3 || a.dot), NR_ERR_ARG, "tgemm: null op or no output");
   NR_REQUIRE(a.x1 && (KB2 == 0 || a.x2), NR_ERR_ARG, "tgemm: missing input segment");
-  // 32-bit byte offsets of the epilogue's asm loads
-  const int64_t maxld = std::max({a.lda, a.ldg, a.ldzd, a.ldy, a.ldyb, a.ldy2, a.ldy3});
-  NR_REQUIRE(a.P * maxld * 4 < ((int64_t)1 << 31), NR_ERR_ARG, "tgemm: epilogue operands exceed 2 GB");
+  // 32-bit byte offsets of the asm loads and stores: the epilogue's tensors and the inputs (the next-tile
+  // prefetch reads x1 at a 32-bit byte offset, load_seg forms a 32-bit float index); P * ld floats is the
+  // extent of a tensor in both layouts (row-major and 16 x 16 blocked)
+  const int64_t maxld = std::max({a.ld1, KB2 > 0 ? a.ld2 : (int64_t)0, a.lda, a.ldg, a.ldzd, a.ldy, a.ldyb, a.ldy2,
+                                  a.ldy3});
+  NR_REQUIRE(a.P * maxld * 4 < ((int64_t)1 << 31), NR_ERR_ARG, "tgemm: an input or epilogue operand exceeds 2 GB");
   if (a.blocked) {  // 16 x 16 blocked tensors: whole blocks of points and columns
     const int64_t lds[9] = {a.ld1, a.ld2, a.ldy, a.ldyb, a.ldy2, a.ldy3, a.lda, a.ldg, a.ldzd};
     bool ok = a.P % 16 == 0 && (a.blocked & ~0x1ff) == 0;
     for (int i = 0; i < 9; ++i) ok = ok && (!(a.blocked & (1 << i)) || (lds[i] > 0 && lds[i] % 16 == 0));
     NR_REQUIRE(ok, NR_ERR_ARG, "tgemm: a blocked tensor needs P and its leading dimension multiples of 16");
+  }
+  bool known = false;  // refused before any HIP call, as the argument errors above
+#define NR_TG_KNOWN(kb, kb2, nbo, nb2, md) \
+  known = known || (KB == kb && KB2 == kb2 && NBO == nbo && NB2 == nb2 && a.mode == md);
+  NR_TG_SHAPES(NR_TG_KNOWN)
+#undef NR_TG_KNOWN
+  if (!known) {
+    set_error("tgemm: unsupported (input blocks, output blocks) shape");
+    return NR_ERR_UNSUPPORTED;
   }
   const int64_t tiles = (a.P + kPointsPerWG - 1) / kPointsPerWG;
   int dev = 0, cus = 256;

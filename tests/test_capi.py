@@ -175,6 +175,49 @@ def test_r05_training_entries_reject_bad_arguments(lib):
     assert rc == -1 and 'ld_small' in lib.nr_last_error().decode()
 
 
+def test_train_gemm_rejects_bad_arguments(lib):
+    """nr_train_gemm checks its arguments before any HIP call (fake device pointers: nothing is
+    dereferenced on the error paths), among them the 32-bit offsets of its inputs: B0 (16 input blocks of
+    a 256-wide tensor, 4 output blocks of a 64-wide one) on 5 M points would wrap the byte offset of x1"""
+    from neurecon_amd import _lib
+
+    def args(**kw):
+        t = _lib.NrTrainGemm()
+        t.op, t.P, t.x1, t.ld1, t.n1, t.y, t.ldy = 0x1000, 1024, 0x10000, 256, 256, 0x20000, 256
+        t.mode, t.yscale = _lib.TG_NONE, 1.0
+        for k, v in kw.items():
+            setattr(t, k, v)
+        return t
+
+    def call(t, shape=(16, 0, 16, 0)):
+        return lib.nr_train_gemm(None if t is None else ctypes.byref(t), *shape, None), lib.nr_last_error().decode()
+    rc, msg = call(None)
+    assert rc == -1 and 'null argument' in msg
+    rc, msg = call(args(y=None))
+    assert rc == -1 and 'no output' in msg
+    rc, msg = call(args(mode=_lib.TG_SOFTPLUS), (18, 4, 16, 0))             # F4 without its second segment
+    assert rc == -1 and 'missing input segment' in msg
+    rc, msg = call(args(), (16, 0, 12, 0))
+    assert rc == -2 and 'unsupported' in msg
+    rc, msg = call(args(mode=_lib.TG_SPADJ, a=0x30000, lda=256), (4, 0, 16, 0))   # a shape of another mode
+    assert rc == -2 and 'unsupported' in msg
+    rc, msg = call(args(P=1000, blocked=_lib.BLK_X1))
+    assert rc == -1 and 'multiples of 16' in msg
+    rc, msg = call(args(blocked=_lib.BLK_Y, ldy=250))
+    assert rc == -1 and 'multiples of 16' in msg
+    # 32-bit byte offsets: P ld 4 of every tensor, the inputs included
+    rc, msg = call(args(P=5_000_000, ld1=256, ldy=64), (16, 0, 4, 0))
+    assert rc == -1 and '2 GB' in msg
+    rc, msg = call(args(P=5_000_000, ld1=256, ldy=64, blocked=_lib.BLK_X1), (16, 0, 4, 0))  # the blocked extent
+    assert rc == -1 and '2 GB' in msg
+    rc, msg = call(args(P=5_000_000, mode=_lib.TG_SOFTPLUS, ld1=64, n1=39, x2=0x40000, ld2=256, n2=39, ldy=64),
+                   (18, 4, 16, 0))                                                             # ... of x2
+    assert rc == -1 and '2 GB' in msg
+    rc, msg = call(args(P=5_000_000, ld1=64, ldy=256), (16, 0, 4, 0))                        # as before: an output
+    assert rc == -1 and '2 GB' in msg
+    assert call(args(P=0))[0] == 0                                                             # empty: no launch
+
+
 def _lib_env_int(name):
     from neurecon_amd import _lib
     return _lib._env_int(name)

@@ -4,9 +4,10 @@ autograd (oracle/train.py, pinned to the reference's own Trainer.forward + backw
 tests/test_oracle_golden.py::test_oracle_train_step_vs_golden) and vs that reference golden.
 
 Bar: |grad - ref| <= 1e-4 |ref| + 1e-5 max|ref| per parameter tensor (components near zero of a
-large gradient), losses 1e-5 relative.  The gradient GEMMs run in fp32 (hipBLASLt); the no-grad
-sample pass runs in the model's precision -- the oracle gets the GPU's sample depths so a flipped
-sampling decision cannot masquerade as a gradient error.
+large gradient), losses 1e-5 relative.  The layer products of the gradient pass run on nr_train_gemm
+(f16x3 nets; tests/test_gpu_tgemm.py holds it to float64 call by call) or nr_gemm32 (fp32 nets), the
+weight gradients on nr_wgrad; the no-grad sample pass runs in the model's precision -- the oracle gets
+the GPU's sample depths so a flipped sampling decision cannot masquerade as a gradient error.
 """
 import os
 import socket
@@ -227,17 +228,21 @@ def _as_golden(ref_grads, g):
     return out
 
 
-def test_sdf_double_backward_vs_autograd():
-    """SdfNabla on its own: random points (ragged P), random upstream gradients for sdf, nablas and
-    the geometry feature -> every SDF-net parameter gradient vs torch autograd (create_graph) on CPU."""
+@pytest.mark.parametrize('precision', ['fp32', 'f16x3'])
+def test_sdf_double_backward_vs_autograd(precision):
+    """SdfNabla (fp32 nets) / SdfNablaTG (f16x3 nets, on nr_train_gemm) on its own: random points (ragged
+    P; f16x3 also P = 2048, where the layer tensors are 16 x 16 blocked), random upstream gradients for sdf,
+    nablas and the geometry feature -> every SDF-net parameter gradient vs torch autograd (create_graph)
+    on CPU."""
     from oracle.nets import SDFNet
     from oracle.train import nablas_graph
     from neurecon_amd import training as T
     sd = wg.neus_state(seed=11)
-    m = neus_model(sd)
+    m = neus_model(sd, precision=precision)
     m.train()
+    assert T.uses_train_gemm(m.implicit_surface) == (precision == 'f16x3')
     torch.manual_seed(3)
-    for P in (1, 130, 2000):
+    for P in (1, 130, 2000) + ((2048,) if precision == 'f16x3' else ()):
         x = torch.randn(P, 3) * 0.7
         gs, gn, gf = torch.randn(P), torch.randn(P, 3), torch.randn(P, 256) * 0.01
         sdp = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith('implicit_surface.')
@@ -257,12 +262,15 @@ def test_sdf_double_backward_vs_autograd():
             assert ok.all(), k
 
 
-def test_radiance_backward_vs_autograd():
+@pytest.mark.parametrize('precision', ['fp32', 'f16x3'])
+def test_radiance_backward_vs_autograd(precision):
+    """RadianceFn (fp32 nets) / RadianceTG (f16x3 nets: the backward on nr_train_gemm) vs CPU autograd"""
     from oracle.nets import RadianceNet
     from neurecon_amd import training as T
     sd = wg.neus_state(seed=11)
-    m = neus_model(sd)
+    m = neus_model(sd, precision=precision)
     m.train()
+    assert T.uses_train_gemm(m.radiance_net) == (precision == 'f16x3')
     torch.manual_seed(4)
     P = 777
     x, v = torch.randn(P, 3), torch.nn.functional.normalize(torch.randn(P, 3), dim=-1)
