@@ -257,7 +257,6 @@ _SIGS = {
     'nr_wgrad': (_c_i, [ctypes.POINTER(NrWgrad), _c_p]),
     'nr_profile_enable': (_c_i, [_c_i]),
     'nr_gemm32': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_i64, _c_i64, _c_i, _c_i, _c_i, _c_p]),
-    'nr_sdf5_enable': (_c_i, [_c_i]),
     'nr_profile_filter': (_c_i, [ctypes.c_char_p]),
     'nr_profile_read': (_c_i, [ctypes.POINTER(NrKernelStat), _c_i, ctypes.POINTER(_c_i)]),
 }
@@ -271,14 +270,6 @@ _lib = None
 class NrError(RuntimeError):
     pass
 
-
-
-def _env_int(name):
-    """integer value of an environment switch (unset, empty or not a number: 0)"""
-    try:
-        return int(os.environ.get(name, '') or 0)
-    except ValueError:
-        return 0
 
 def lib():
     """Load libnrhip.so (raises if absent: the HIP path is the only path)."""
@@ -294,8 +285,6 @@ def lib():
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args
-            if _env_int('NR_SDF5'):  # kernel selection (nr_sdf5_enable), for A/B runs
-                L.nr_sdf5_enable(_env_int('NR_SDF5'))
             _lib = L
     return _lib
 

@@ -76,10 +76,6 @@ SdfLayout sdf_layout(const NrSdfDesc& d) {
   off = align256(off + 256 * 4);
   L.misc_off = (uint32_t)off;
   off = align256(off + 16);
-  if (g_sdf5_pack && L.prec == NR_PREC_F16X3 && !L.siren) {  // the ops again in the 32x32x16 layout (nr_sdf5.hip)
-    L.l32_off = (uint32_t)off;
-    off = align256(off + L.scale_off);
-  }
   L.total = (uint32_t)off;
   return L;
 }
@@ -814,17 +810,10 @@ int nr_sdf_pack(const NrSdfDesc* d, const float* const* W, const float* const* b
   ops[B0] = mkop(W[0], nullptr, ROWS(0), in0, 1, seg(4, 0, in0), none(), seg(16, 0, 256), none(), 1.0f, prec, wmax + B0);
   float* bound = (float*)(P + L.bound_off);
   for (int i = 0; i < kSdfOps; ++i) ops[i].bound = bound + 2 * i;
-  ops[F7].aux = W[8];  // sdf row W8[0, :] rides with F7's chunks (v2 pipeline's running dot product)
+  ops[F7].aux = W[8];  // sdf row W8[0, :] rides with F7's chunks (F7Epi4's running dot product)
   char* dst[kSdfOps];
   for (int i = 0; i < kSdfOps; ++i) dst[i] = P + L.op_off[i];
   if ((rc = launch_pack_ops(ops, dst, kSdfOps, st))) return rc;
-  if (L.l32_off) {  // the 32x32x16 copy of the forward ops (same scales and bounds, rewritten identically)
-    for (int i = 0; i <= F8; ++i) {
-      ops[i].l32 = 1;
-      dst[i] = P + L.l32_off + L.op_off[i];
-    }
-    if ((rc = launch_pack_ops(ops, dst, F8 + 1, st))) return rc;
-  }
   if ((rc = launch_pack_vec(W[8], 0, 256, 256, P + L.w8row0_off, st))) return rc;
   if ((rc = launch_pack_vec(b[8], 0, 1, 4, P + L.misc_off, st))) return rc;
   return NR_OK;

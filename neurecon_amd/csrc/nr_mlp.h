@@ -14,17 +14,10 @@ constexpr size_t kScratchPerWG = (size_t)kWaves * 8 * 16 * 64 * 16;  // exp(100z
 // 2^-L = 1 - softplus'(z) (per chunk [block 2][column][lane] x 12 B: 8 chunks x 1536 B = 12 KB per
 // layer), layer 7 holds d sdf / d z7 (and, during the forward, the parked embedding) in fp32
 // ([block 16][column][lane] x 16 B); 100 KB instead of 8 x 16 KB of fp32 slabs
-// NR_SLAB32: each code as the fp32 F = 2^23 + round(c 2^23) (bits 0x4B000000 | code), 16 B per 4 codes:
-// the forward forms it with one fma and the reverse pass softplus' = 2 - F 2^-23 with one more, instead
-// of packing / unpacking 24-bit fields (128 KB per column)
-#ifdef NR_SLAB32
-constexpr int kSlabVB = 16;                             // slab bytes per lane and 4 codes
-#else
-constexpr int kSlabVB = 12;
-#endif
-constexpr int kSlab24Chunk = 2 * 64 * kSlabVB;          // one chunk of one column: 1536 B (2 KB with NR_SLAB32)
-constexpr int kSlab24Layer = 8 * kSlab24Chunk;          // 12 KB (16 KB)
-constexpr int kSlabColBytes = 7 * kSlab24Layer + 16 * 64 * 16;  // 100 KB (128 KB) per column (deferred tile)
+constexpr int kSlabVB = 12;                             // slab bytes per lane and 4 codes
+constexpr int kSlab24Chunk = 2 * 64 * kSlabVB;          // one chunk of one column: 1536 B
+constexpr int kSlab24Layer = 8 * kSlab24Chunk;          // 12 KB
+constexpr int kSlabColBytes = 7 * kSlab24Layer + 16 * 64 * 16;  // 100 KB per column (deferred tile)
 
 // SDF GEMM ops in stream order (forward F*, feature F8, backward B*)
 enum SdfOp { F0, F1, F2, F3, F4, F5, F6, F7, F8, B7, B6, B5, B4, B3, B2, B1, B0, kSdfOps };
@@ -54,8 +47,6 @@ struct SdfLayout {
   uint32_t bound_off;          // [kSdfOps][2] max row L1 norm, max |bias| per op (f16x3 operand scales)
   uint32_t w8row0_off;         // sdf row of the last layer [256]
   uint32_t misc_off;           // [0] = sdf bias
-  uint32_t l32_off;            // f16x3 softplus nets: the ops again in the 32x32x16 layout (nr_sdf5.hip),
-                               // at l32_off + op_off[i]; 0: none
   uint32_t total;
   int prec;
   int siren;                   // op_off / op_bytes indexed by SirenOp
@@ -129,7 +120,6 @@ struct PackOp {
   const float* bias2;  //   ... and its bias
   int64_t wn2;
   int ld2;
-  int l32;             // f16x3: the 32x32x16 A layout of nr_sdf5.hip instead of the 16x16x32 one
 };
 
 int launch_pack_op(const PackOp& op, char* dst, hipStream_t stream);
@@ -139,11 +129,6 @@ int launch_pack_vec(const float* src, int off, int nvalid, int n, char* dst, hip
 int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
                float* feature, int nfreq, void* ws, size_t ws_bytes, hipStream_t stream,
                const int* P_dev = nullptr, int P_mult = 0);  // P_dev: device count, P_eff = min(P, *P_dev * P_mult)
-// SDF forward (sdf only) on the 32x32x16 kernel (nr_sdf5.hip): needs L.l32_off
-int launch_sdf5_fwd(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, int nfreq,
-                    hipStream_t stream, const int* P_dev, int P_mult);
-extern int g_sdf5;             // route launch_sdf's forward-only f16x3 launches to it (nr_sdf5_enable)
-extern const int g_sdf5_pack;  // $NR_SDF5 (a nonzero integer) at load: the layout carries the 32x32x16 copy
 // deferred sample nablas (sdf4_kernel STAGE 1 / 2): stage 1 = sdf + slabs per 16-point tile into
 // `slabs` (P/16 x kSlabColBytes); stage 2 = nablas of the tiles tiles[0 .. *n_tiles) from their slabs;
 // stage 4 = nablas of the points tiles[0 .. *n_tiles) (neus_point_list's layout: 16-aligned segments of

@@ -17,7 +17,6 @@
 //  * Everything per point (embedding, nabla chain rule through sin/cos, sdf row dot product,
 //    sigmoid head) is VALU work in the same kernel.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include "nr_common.h"
 #include "nr_mlp.h"
@@ -121,13 +120,6 @@ __device__ __forceinline__ uint32_t lds_u32(const void* p) {
   return (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
 }
 
-// chunk loops: rolled (push2 rotates the outputs) unless NR_EXP_UNROLL (experiment)
-#ifdef NR_EXP_UNROLL
-#define NR_CHUNK_UNROLL _Pragma("unroll")
-#else
-#define NR_CHUNK_UNROLL _Pragma("unroll 1")
-#endif
-
 constexpr int kRing = 3;
 constexpr int kSlabChunk = kWaves * 2 * 64 * 16;  // softplus' of 2 blocks for every wave: 16 KB
 
@@ -140,9 +132,6 @@ struct WStream {
   int ecur;    // slab slot of the chunk being computed
   __device__ __forceinline__ static int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
   __device__ __forceinline__ int dma(const char* gsrc, int bytes, int slot) {
-#ifdef NR_EXP_NO_DMA  // timing experiment only: weights are not streamed (results are garbage)
-    return 0;
-#endif
     const int wave = wave_id();
     const uint32_t voff = (threadIdx.x & 63) * 16;
     const char* g = uniform_ptr(gsrc);
@@ -165,14 +154,12 @@ struct WStream {
   __device__ __forceinline__ void none() { pend = 0; }
   // softplus' blocks (b, b+1) of this wave's slab for the NEXT chunk (before issue())
   __device__ __forceinline__ void slab_next(const float4* e, int b) {
-#ifndef NR_EXP_NO_ELOAD
     const int wave = wave_id();
     const uint32_t voff = (threadIdx.x & 63) * 16;
     const char* g = (const char*)uniform_ptr(e + b * 64);
     const uint32_t base = __builtin_amdgcn_readfirstlane(lds_u32(slab) + (uint32_t)((ecur ^ 1) * kSlabChunk + wave * 2048));
     glds16s(g, voff, base);
     glds16s(g + 1024, voff, base + 1024);
-#endif
   }
   // ... or for the CURRENT chunk, waiting for it (once per tile, before the first reverse op)
   __device__ __forceinline__ void slab_now(const float4* e, int b) {
@@ -187,9 +174,7 @@ struct WStream {
   __device__ __forceinline__ const float4* buf() const { return (const float4*)(lds + cur * CBMAX); }
   __device__ __forceinline__ void flip() {
     wait_vmcnt(pend);  // everything older than the newest chunk's DMA has landed (this wave)
-#ifndef NR_EXP_NO_BARRIER  // timing experiment: waves drift apart (results are garbage)
     __syncthreads();   // ... for every wave
-#endif
     cur = (cur + 1) % kRing;
     ecur ^= 1;
   }
@@ -263,9 +248,6 @@ __device__ __forceinline__ void push2cat(float4 (&Y)[16], float4 (&Z)[4], float4
 //  P = NR_PREC_F16X3: hardware v_exp_f32 / v_log_f32 / v_rcp_f32 (~1e-6 rel), for the fast mode.
 template <int P>
 __device__ __forceinline__ void softplus_fwd(float z, float& y, float& e) {
-#ifdef NR_EXP_NO_SOFTPLUS  // timing experiment: activation skipped (results are garbage)
-  y = z; e = z; return;
-#endif
   const float t = fmul(z, 100.0f);
   const bool lin = t > 20.0f;
   if constexpr (P == NR_PREC_FP32) {
@@ -344,16 +326,6 @@ __device__ __forceinline__ float make_b16(const float4 (&X)[16], const float4 (&
                                           f16x8 (&bl)[12]) {
   constexpr int KB = KBX + KBE;
   static_assert(KB % 2 == 0 && KB <= 24, "bad block count");
-#ifdef NR_EXP_NO_SPLIT  // timing experiment: operands reinterpreted, not split (results are garbage)
-#pragma unroll
-  for (int s = 0; s < KB / 2; ++s) {
-    const float4 v0 = 2 * s < KBX ? X[2 * s < KBX ? 2 * s : 0] : E[2 * s < KBX ? 0 : 2 * s - KBX];
-    const float4 v1 = 2 * s + 1 < KBX ? X[2 * s + 1 < KBX ? 2 * s + 1 : 0] : E[2 * s + 1 < KBX ? 0 : 2 * s + 1 - KBX];
-    bh[s] = as_h8(v0);
-    bl[s] = as_h8(v1);
-  }
-  return 1.0f;
-#endif
   float m = 0.0f;
 #pragma unroll
   for (int b = 0; b < KBX; ++b) m = fmaxf(m, amax4(X[b]));
@@ -425,14 +397,12 @@ __device__ __forceinline__ void gemm_fwd(WS& ws, const char* __restrict__ op, co
   auto drain = [&]() {
     if (pc >= 0) {
       if constexpr (ACT == ACT_SOFTPLUS || ACT == ACT_SINE) {
-#ifndef NR_EXP_NO_ESTORE  // timing experiment: skip the e-slab stores
         if (e_out) {  // streamed: non-temporal so the slab does not evict the weights from L2
           using gf4 = __attribute__((address_space(1))) f32x4;
           gf4* eb = (gf4*)uniform_ptr(e_out + (2 * pc) * 64);
           __builtin_nontemporal_store(tof(p0), eb + lane);
           __builtin_nontemporal_store(tof(p1), eb + 64 + lane);
         }
-#endif
       } else {
         if (feat_out && feat_ok) {  // row-major [P][256] feature rows of that chunk
           *(float4*)(feat_out + (2 * pc) * 16 + g * 4) = p0;
@@ -442,7 +412,7 @@ __device__ __forceinline__ void gemm_fwd(WS& ws, const char* __restrict__ op, co
     }
     pc = -1;
   };
-NR_CHUNK_UNROLL
+#pragma unroll 1
   for (int c = 0; c < NCH; ++c) {
     drain();
     if (c + 2 < NCH) ws.issue(op + (c + 2) * CB, CB);
@@ -509,7 +479,7 @@ __device__ __forceinline__ void gemm_bwd(WS& ws, const char* __restrict__ op, co
   f16x8 bh[12], bl[12];
   float ginv = 1.0f;
   if constexpr (P == NR_PREC_F16X3) ginv = make_b16<KBG, 0, 4>(G, dummy, bh, bl);
-NR_CHUNK_UNROLL
+#pragma unroll 1
   for (int c = 0; c < NCH; ++c) {
     const bool main = 2 * c < NBO1;
     if (2 * c + 2 < NBO1) {
@@ -534,11 +504,7 @@ NR_CHUNK_UNROLL
     if (main) {
       if (e_cur) {
         const float4* eb = ws.slab_cur();
-#ifdef NR_EXP_NO_ELOAD
-        const float4 e0 = make_float4(1.f, 1.f, 1.f, 1.f), e1 = e0;
-#else
         const float4 e0 = eb[lane], e1 = eb[64 + lane];
-#endif
         y0 = make_float4(act_bwd<P, ACTB>(y0.x, e0.x), act_bwd<P, ACTB>(y0.y, e0.y), act_bwd<P, ACTB>(y0.z, e0.z),
                          act_bwd<P, ACTB>(y0.w, e0.w));
         y1 = make_float4(act_bwd<P, ACTB>(y1.x, e1.x), act_bwd<P, ACTB>(y1.y, e1.y), act_bwd<P, ACTB>(y1.z, e1.z),
@@ -740,14 +706,10 @@ __global__ __launch_bounds__(kThreads) void sdf_kernel(SdfKArgs a) {
 
 // =============================================================================================
 // f16x3 operand helpers of the v3 SDF pipeline (sdf4_kernel, below)
-// NR_SDF4_NC: 16-point MFMA columns per wave of sdf4_kernel.  1 (default): 8 waves of 16 points, two
-// waves per SIMD with up to 256 registers each, every operand in VGPRs (no AGPR moves); the two
-// waves of a SIMD hide each other's DMA / LDS / barrier stalls.  2: 4 waves of 32 points, one per
-// SIMD with 512 registers, B operands parked in AGPRs; each weight fragment read from LDS feeds
-// both columns (half the LDS read traffic).  Measured on config (b): 1 is ~5 % faster.
-#ifndef NR_SDF4_NC
-#define NR_SDF4_NC 1
-#endif
+// A wave of sdf4_kernel owns kNC = 1 16-point MFMA column: 8 waves of 16 points, two waves per SIMD
+// with up to 256 registers each, every operand in VGPRs (no AGPR moves); the two waves of a SIMD hide
+// each other's DMA / LDS / barrier stalls.  Measured on config (b): ~5 % faster than 4 waves of 32
+// points (one per SIMD, B operands in AGPRs, each weight fragment feeding two columns).
 // =============================================================================================
 // What changes against sdf_kernel<F16X3> (which stays the reference design for the radiance and
 // NeRF++ kernels):
@@ -790,9 +752,7 @@ __device__ __forceinline__ void split8s(float4 a, float4 b, float sc, f16x8& h, 
 }
 // ... with both halves from v_fma_mix, written straight into the packed f16 pairs: hi = f16(v*sc)
 // (one rounding of the exact product), lo = f16(v*sc - hi); no packed-fp32 multiply (v_pk_mul_f32
-// issued beside MFMAs costs ~22 cycles more than scalar VALU, MI355X_MICROARCH.md).  With 32-point
-// waves (NR_SDF4_NC 2) the pairs are parked in AGPRs: B operands are read only by MFMAs, which take
-// AGPR sources directly
+// issued beside MFMAs costs ~22 cycles more than scalar VALU, MI355X_MICROARCH.md)
 __device__ __forceinline__ void split8a(float4 a, float4 b, float sc, f16x8& h, f16x8& l) {
   const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
   uint32_t hw[4], lw[4];
@@ -811,9 +771,6 @@ __device__ __forceinline__ void split8a(float4 a, float4 b, float sc, f16x8& h, 
   }
   h = __builtin_bit_cast(f16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
   l = __builtin_bit_cast(f16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
-#if NR_SDF4_NC == 2 && !defined(NR_SPLIT_VGPR)
-  asm volatile("" : "+a"(h), "+a"(l));
-#endif
 }
 __device__ __forceinline__ float max3abs(float m, float a, float b) {
   return __builtin_fmaxf(m, __builtin_fmaxf(fabsf(a), fabsf(b)));  // -> v_max3_f32 with |.| modifiers
@@ -874,15 +831,13 @@ using gf4 = __attribute__((address_space(1))) f32x4;
 // =============================================================================================
 // f16x3 SDF pipeline v3 (sdf4_kernel): kNC 16-point columns per wave, 128-point tile
 // =============================================================================================
-// * 8 waves x 16 points (two per SIMD, 256 registers each) or 4 waves x 32 points (one per SIMD,
-//   512 registers, each A fragment read from LDS feeds both columns): either way the B operands of
-//   the op being computed AND of the op being produced stay in registers.
+// * 8 waves x 16 points (two per SIMD, 256 registers each): the B operands of the op being computed
+//   AND of the op being produced stay in registers.
 // * Chunk c's epilogue (bias, activation, slab I/O, per-chunk operand split) is issued in the same
 //   basic block as chunk c+1's MFMAs, so the wave's VALU work fills the matrix core's issue gaps.
 // * The operand split uses per-point power-of-two scales fixed before the op runs, from a bound on
-//   its outputs (see the v2 notes above: split8s / bound_scale / softplus3).
-constexpr int kNC = NR_SDF4_NC;   // 16-point MFMA columns per wave (1: two waves per SIMD; 2: one)
-static_assert(kNC == 1 || kNC == 2, "columns per wave");
+//   its outputs (see the operand-helper notes above: split8a / bound_scale).
+constexpr int kNC = 1;            // 16-point MFMA columns per wave (two waves per SIMD)
 constexpr int kW4 = 8 / kNC;      // waves per workgroup: the tile stays 128 points
 constexpr int kT4 = 64 * kW4;
 constexpr int kWPE = kW4 / 4;     // waves per SIMD
@@ -890,10 +845,7 @@ constexpr int kWPE = kW4 / 4;     // waves per SIMD
 // global_load_lds_dwordx3 lands lane l's 12 B at l x 16, the 4th dword untouched: tools/probes/ldsdma_x3)
 constexpr int kSlabW = 2 * kNC * 1024;
 constexpr int kSlab4 = kW4 * kSlabW;        // ... of the workgroup: 16 KB
-#ifndef NR_DMA_LOADERS
-#define NR_DMA_LOADERS (8 / NR_SDF4_NC)
-#endif
-constexpr int kLoad = NR_DMA_LOADERS;  // waves that issue the weight stream (the last kLoad)
+constexpr int kLoad = 8;                    // waves that issue the weight stream (the last kLoad)
 static_assert(kLoad >= 1 && kLoad <= kW4, "loader waves");
 
 // Deferred stores of one chunk (up to 4 x 16 B per lane), issued at the start of the next chunk
@@ -909,7 +861,6 @@ struct Pend4 {
   bool b96;       // 12-byte stores (24-bit slab codes)
   // global_store_dwordx4 with an SGPR base and a 32-bit VGPR byte offset (saddr form), from asm:
   // compiler-built 64-bit per-lane addresses get hoisted out of the tile loop and spilled
-  __device__ __forceinline__ int pending() const { return base ? n : 0; }
   __device__ __forceinline__ int flush() {
     int issued = 0;
     if (base) {
@@ -944,24 +895,12 @@ struct Pend4 {
   }
 };
 
-constexpr int kSlabRing = 3;
-// weight-ring slots of the forward-only sdf4_kernel launches (4; 3 = the r04 build, for A/B)
-#ifndef NR_FWD_RING
-#define NR_FWD_RING 4
-#endif
+constexpr int kSlabRing = 3;  // softplus' slabs in LDS: one being read, one landing, one being staged
+constexpr int kFwdRing = 4;   // weight-ring slots of the forward-only sdf4_kernel launches
 // cache policy of the forward softplus slab stores (read back by the reverse pass of the same tile)
-#ifndef NR_SLAB_NT
-#define NR_SLAB_NT true
-#endif
-// ... of the slab loads staged back into LDS (read once: nt keeps them from evicting the weight
-// stream's lines in L2; 3.80 -> 3.74 ms per 524 k-point nabla + feature launch)
-#ifndef NR_SLAB_LD_POL
-#define NR_SLAB_LD_POL " nt"
-#endif
+constexpr bool kSlabNT = true;
 // ... of the geometry-feature and d sdf / d z7 stores
-#ifndef NR_FEAT_NT
-#define NR_FEAT_NT false
-#endif  // softplus' slabs in LDS: one being read, one landing, one being staged
+constexpr bool kFeatNT = false;
 
 // RING: weight-ring slots, issued RING - 1 chunks ahead of the chunk being computed.  3 wherever the
 // slab ring shares the LDS (reverse passes); 4 in the forward-only launches, whose LDS holds the
@@ -998,9 +937,6 @@ struct WStream4 {
   // M0 setting: the instruction offset steps the global and the LDS address together.
   template <int BYTES>
   __device__ __forceinline__ void dma(const char* gsrc, int slot) {
-#ifdef NR_EXP_NO_DMA
-    return;
-#endif
     constexpr int NB = BYTES / 1024, NPW = pieces<BYTES>();
     const int wave = loader();
     if (wave < 0) return;
@@ -1044,19 +980,6 @@ struct WStream4 {
         glds16m(gj, voff, mj);
     }
   }
-  // piece j (0 <= j < pieces<BYTES>()) of this wave's run of a chunk, into the slot issue() fills
-  template <int BYTES>
-  __device__ __forceinline__ void dma_piece(const char* gsrc, int j) {
-#ifdef NR_EXP_NO_DMA
-    return;
-#endif
-    constexpr int NB = BYTES / 1024, NPW = pieces<BYTES>();
-    if (loader() < 0) return;
-    const int first = __builtin_amdgcn_readfirstlane(min(loader() * NPW, NB - NPW)) + j;
-    const int slot = ahead_slot();
-    glds16m(uniform_ptr(gsrc) + first * 1024, (threadIdx.x & 63) * 16,
-            __builtin_amdgcn_readfirstlane(lds_u32(lds) + (uint32_t)(slot * CBMAX) + (uint32_t)(first * 1024)));
-  }
   template <int B0, int B1>
   __device__ __forceinline__ void start(const char* g0, const char* g1) {
     static_assert(RING == 3, "start: the first RING - 1 chunks");
@@ -1084,15 +1007,8 @@ struct WStream4 {
   }
   template <int BYTES>
   __device__ __forceinline__ void issue(const char* gsrc) { dma<BYTES>(gsrc, ahead_slot()); }
-  // after a mid-chunk flip (cur already names the next chunk's slot): the chunk after that
-  template <int BYTES>
-  __device__ __forceinline__ void issue_next(const char* gsrc) {
-    static_assert(RING == 3, "NR_MID_FLIP: 3-slot ring");
-    dma<BYTES>(gsrc, next3(cur));
-  }
-  // this wave's softplus' slab of chunk c (blocks 2c, 2c+1, all kNC columns: 2 or 4 KB contiguous) ->
-  // the next slab slot; one M0 setting, the instruction offset steps global and LDS address together.
-  // Staged two chunk-iterations before the epilogue that reads it.  Returns the DMA instructions issued.
+  // this wave's softplus' slab of chunk c (blocks 2c, 2c+1, all kNC columns: 2 kNC pieces, contiguous in
+  // global memory) -> the next slab slot.  Staged two chunk-iterations before the epilogue that reads it.  Returns the DMA instructions issued.
   // e: byte base of the layer's slab (24-bit codes, kSlab24Chunk per column and chunk)
   __device__ __forceinline__ int stage_slab(const float4* e, int c) {
     return stage_slab(e, c, (threadIdx.x & 63) * kSlabVB);
@@ -1100,33 +1016,22 @@ struct WStream4 {
   // voff: this lane's byte offset from e (lane x kSlabVB; the compacted reverse pass gathers each lane's
   // codes from its point's own tile)
   __device__ __forceinline__ int stage_slab(const float4* e, int c, uint32_t voff) {
-#ifdef NR_EXP_NO_ELOAD  // timing experiment: softplus' slab not read back
-    return 0;
-#endif
     // global: 768 B per piece (64 lanes x 12 B); LDS: 1 KB per piece (lane stride 16 B), so each piece
-    // gets its own global base and M0 (the instruction offset would step both by the same amount)
+    // gets its own global base and M0 (the instruction offset would step both by the same amount).
+    // nt: the codes are read once, so they should not evict the weight stream's lines from L2
+    // (3.80 -> 3.74 ms per 524 k-point nabla + feature launch)
     const char* g = uniform_ptr((const char*)e + kNC * kSlab24Chunk * c);
     const uint32_t base =
         __builtin_amdgcn_readfirstlane(lds_u32(slab) + (uint32_t)(es * kSlab4 + wave_id() * kSlabW));
 #pragma unroll
     for (int piece = 0; piece < 2 * kNC; ++piece) {
-#ifdef NR_SLAB32
-      const char* gp = g + piece * 1024;
-      asm volatile(
-          "s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-          "global_load_lds_dwordx4 %0, %1" NR_SLAB_LD_POL
-          :
-          : "v"(voff), "s"(gp), "s"(base + piece * 1024)
-          : "memory", "m0");
-#else
       const char* gp = g + piece * 768;
       asm volatile(
           "s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-          "global_load_lds_dwordx3 %0, %1" NR_SLAB_LD_POL
+          "global_load_lds_dwordx3 %0, %1 nt"
           :
           : "v"(voff), "s"(gp), "s"(base + piece * 1024)
           : "memory", "m0");
-#endif
     }
     es = next3(es);
     return 2 * kNC;
@@ -1154,16 +1059,12 @@ struct WStream4 {
     } else {
       wait_vmcnt(n);
     }
-#ifndef NR_EXP_NO_BARRIER
     __syncthreads();
-#endif
     cur = nextr(cur);
   }
   // the caller has waited for everything the next chunk needs (tgemm_kernel's counted waits)
   __device__ __forceinline__ void flip_nowait() {
-#ifndef NR_EXP_NO_BARRIER
     __syncthreads();
-#endif
     cur = nextr(cur);
   }
 };
@@ -1173,13 +1074,7 @@ struct WStream4 {
 // issue).  stage(s) is VALU work of the previous chunk's epilogue placed in k-step s's scheduling
 // region, so it fills the matrix core's issue gaps instead of running before or after the MFMAs.
 __device__ __forceinline__ f16x8 rd_frag(const float4* __restrict__ A, int i, int lane) {
-#ifdef NR_EXP_NO_AREAD  // timing experiment: weight fragments not read from LDS (results are garbage)
-  uint4 v = make_uint4(i, i, i, i);
-  asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-  return __builtin_bit_cast(f16x8, v);
-#else
   return as_h8(A[i * 64 + lane]);
-#endif
 }
 template <int NS, class Stage>
 __device__ __forceinline__ void mma4(const float4* __restrict__ A, const f16x8 (&bh)[kNC][12],
@@ -1196,10 +1091,6 @@ __device__ __forceinline__ void mma4(const float4* __restrict__ A, const f16x8 (
       nl1 = rd_frag(A, (NS + s + 1) * 2 + 1, lane);
     }
     stage(s);
-#ifdef NR_EXP_NO_MFMA  // timing experiment: fragments read, no matrix work (results are garbage)
-    asm volatile("" : : "v"(h0), "v"(l0), "v"(h1), "v"(l1));
-    continue;
-#endif
 #pragma unroll
     for (int q = 0; q < kNC; ++q) {
       acc[q][0] = mfma16h(l0, bh[q][s], acc[q][0]);
@@ -1239,7 +1130,7 @@ constexpr float kT = 144.26944f;
 constexpr float kC = 0.0069314749f;
 
 #ifdef NR_EXP_STAMPS
-// timing experiment: per-wave shader-clock totals of the four phases of a chunk iteration (VMEM
+// stamps build: per-wave shader-clock totals of the four phases of a chunk iteration (VMEM
 // issue, MFMA loop + epilogue stages, bias + vmcnt wait, barrier), copied out at the end of the launch
 constexpr int kStampPh = 6;  // 4 phases + iteration count (tgemm_kernel: tile start) + tgemm's epilogue
 __device__ unsigned long long g_nr_stamps[2048 * 8 * kStampPh];
@@ -1275,20 +1166,6 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
     asm volatile("" : "+s"(opc), "+s"(nxc));
     NR_STAMP(t0);
     int npend = 0;
-#ifdef NR_DMA_SPREAD  // the chunk-two-ahead's pieces go out one per k-step region, beside the MFMAs
-    static_assert(LA == 2, "NR_DMA_SPREAD: 3-slot ring");
-    const char* dsrc = nullptr;
-    int dkind = 0;
-    if (c + 2 < NCH) {
-      dsrc = opc + (c + 2) * CB;
-      dkind = 1;
-      npend = WS::template npieces<CB>();
-    } else if (nxc) {
-      dsrc = nxc + (c + 2 - NCH) * NXT_CB;
-      dkind = 2;
-      npend = WS::template npieces<NXT_CB>();
-    }
-#elif !defined(NR_MID_FLIP)
     if (c + LA < NCH) {
       ws.template issue<CB>(opc + (c + LA) * CB);
       npend = WS::template npieces<CB>();
@@ -1296,52 +1173,15 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
       ws.template issue<NXT_CB>(nxc + (c + LA - NCH) * NXT_CB);
       npend = WS::template npieces<NXT_CB>();
     }
-#endif
     npend += pre(c);
-#ifdef NR_VMEM_SPREAD  // the previous chunk's stores go out inside the MFMA loop (k-step region 0)
-    npend += pd.pending();
-#else
     // the previous chunk's stores go out after this chunk's DMA: this chunk's flip does not wait for
     // them (the next one does, two chunk-times after issue)
     npend += pd.flush();
-#endif
     NR_STAMP(t1);
     const float4* A = ws.buf();
     f32x4 acc[kNC][2] = {};
     // the previous chunk's epilogue, 8 stages spread over this chunk's KB/2 k-steps
     mma4<KB / 2>(A, bh, bl, acc, lane, [&](int st) {
-#ifdef NR_MID_FLIP
-      // the flip sits in the middle of the chunk's MFMA stream: waves reach the barrier with MFMAs
-      // still in the pipe, and the next chunk starts without one.  The wait covers chunk c+1's
-      // weights (issued at the previous chunk's flip); everything issued since is this iteration's.
-      // Then chunk c+2 goes into the slot chunk c-1 left (every wave is past it).
-      if (st == KB / 4) {
-        ws.flip(npend);
-        if (c + 2 < NCH) ws.template issue_next<CB>(opc + (c + 2) * CB);
-        else if (nxc) ws.template issue_next<NXT_CB>(nxc + (c + 2 - NCH) * NXT_CB);
-      }
-#endif
-#ifdef NR_VMEM_SPREAD
-      if (st == 0) pd.flush();
-#endif
-#ifdef NR_DMA_SPREAD
-      {
-        constexpr int NS = KB / 2, N1 = WS::template pieces<CB>(), N2 = WS::template pieces<NXT_CB>();
-        if (dkind == 1) {
-#pragma unroll
-          for (int j = 0; j < N1; ++j)
-            if (j * NS / N1 == st) ws.template dma_piece<CB>(dsrc, j);
-        } else if (dkind == 2) {
-#pragma unroll
-          for (int j = 0; j < N2; ++j)
-            if (j * NS / N2 == st) ws.template dma_piece<NXT_CB>(dsrc, j);
-        }
-      }
-#endif
-#ifdef NR_EXP_NO_EPI
-      if (c > 0 && st == 7) epi(c - 1, zq, 7);
-      return;
-#endif
       if (c > 0) {
 #pragma unroll
         for (int e = 0; e < 8; ++e)
@@ -1362,23 +1202,17 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
       zq.aux[0] = A[2 * KB * 64 + 16 + g];
       zq.aux[1] = A[2 * KB * 64 + 20 + g];
     }
-#ifdef NR_EXP_NO_EPI  // keep the MFMAs alive (their results would otherwise be dead code)
-#pragma unroll
-    for (int q = 0; q < kNC; ++q) asm volatile("" : : "v"(tof(zq.z[q][0])), "v"(tof(zq.z[q][1])));
-#endif
 #ifdef NR_EXP_STAMPS
     wait_vmcnt(npend);
     NR_STAMP(t3);
-#ifndef NR_MID_FLIP
     ws.flip(npend);
-#endif
     NR_STAMP(t4);
     stamp_add(0, t1 - t0);
     stamp_add(1, t2 - t1);
     stamp_add(2, t3 - t2);
     stamp_add(3, t4 - t3);
     stamp_add(4, 1);
-#elif !defined(NR_MID_FLIP)
+#else
     ws.flip(npend);
 #endif
   }
@@ -1416,34 +1250,15 @@ __device__ __forceinline__ void pend_chunk(Pend4& pd, float4* base, int first_bl
 // for the reverse pass's staging DMA)
 __device__ __forceinline__ void pend_chunk24(Pend4& pd, float4* layer, int c, int lane, bool nt) {
   const uint32_t l = opaque_lane(lane);
-#ifdef NR_SLAB32  // float4 indices, 16 B stores
-#pragma unroll
-  for (int i = 0; i < 2 * kNC; ++i) pd.o[i] = (uint32_t)(c * kNC * kSlab24Chunk / 16) + (uint32_t)i * 64 + l;
-  pd.put(layer, 2 * kNC, nt, false);
-#else
 #pragma unroll
   for (int i = 0; i < 2 * kNC; ++i) pd.o[i] = (uint32_t)(c * kNC * kSlab24Chunk) + ((uint32_t)i * 64 + l) * 12u;
   pd.put(layer, 2 * kNC, nt, true);
-#endif
 }
 // softplus' = 1 - 2^-L is kept as the 24-bit code of c = 2^-L = 1 / (1 + 2^t): u = floor(c 2^23 + 0.5)
 // (c in [0, 1], 2^23 fits in 24 bits).  The code's absolute error 2^-24 matches fp32's rounding of
 // softplus' near 1 (and of the old 1 - 2^-L cancellation near 0); exact 1 (u = 0) wherever 2^-L < 2^-24,
 // which covers torch's linear branch (100 z > 20: 2^-L < 2^-28.8).  4 codes -> 3 dwords.
 __device__ __forceinline__ uint32_t code24(float c) { return (uint32_t)__builtin_fmaf(c, 8388608.0f, 0.5f); }
-// NR_SLAB32: F = 2^23 + round(c 2^23) in one fma (c 2^23 + 2^23 lies in [2^23, 2^24], where fp32's spacing
-// is 1; c = 1 gives 2^24); the reverse pass's softplus' = 2 - F 2^-23 = 1 - round(c 2^23) 2^-23 is exact
-// (F 2^-23 in [1, 2], Sterbenz), then one multiply by g
-__device__ __forceinline__ float4 code32(float c0, float c1, float c2, float c3) {
-  constexpr float k = 8388608.0f;
-  return make_float4(__builtin_fmaf(c0, k, k), __builtin_fmaf(c1, k, k), __builtin_fmaf(c2, k, k),
-                     __builtin_fmaf(c3, k, k));
-}
-__device__ __forceinline__ float4 code32_mul(float4 F, float4 g) {
-  constexpr float k = -1.0f / 8388608.0f;
-  return make_float4(g.x * __builtin_fmaf(F.x, k, 2.0f), g.y * __builtin_fmaf(F.y, k, 2.0f),
-                     g.z * __builtin_fmaf(F.z, k, 2.0f), g.w * __builtin_fmaf(F.w, k, 2.0f));
-}
 __device__ __forceinline__ float4 pack24(float c0, float c1, float c2, float c3) {
   const uint32_t u0 = code24(c0), u1 = code24(c1), u2 = code24(c2), u3 = code24(c3);
   return make_float4(__uint_as_float(u0 | (u1 << 24)), __uint_as_float((u1 >> 8) | (u2 << 16)),
@@ -1473,13 +1288,6 @@ __device__ __forceinline__ float4 unpack24_mul(uint32_t w0, uint32_t w1, uint32_
 // The running max tracks max(L, t) >= 0; finish() scales it by ln2/100.
 
 template <bool NABLA>
-#ifdef NR_EXP_NO_TRANS  // timing experiment: epilogue transcendentals replaced by moves (results are garbage)
-#define NR_EXP2(x) (x)
-#define NR_LOG2(x) (x)
-#else
-#define NR_EXP2(x) __builtin_amdgcn_exp2f(x)
-#define NR_LOG2(x) __builtin_amdgcn_logf(x)
-#endif
 struct FwdEpi4 {
   static constexpr int NV = 8 * kNC;  // values per lane and chunk
   f16x8 (&oh)[kNC][12];
@@ -1501,15 +1309,15 @@ struct FwdEpi4 {
       for (int i = 0; i < NV; ++i) e[i] = fminf(zval(zz, i), 126.0f);
     } else if (st == 1) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) e[i] = NR_EXP2(e[i]);
+      for (int i = 0; i < NV; ++i) e[i] = __builtin_amdgcn_exp2f(e[i]);
     } else if (st == 2) {
 #pragma unroll
       for (int i = 0; i < NV; ++i) e[i] = e[i] + 1.0f;
 #pragma unroll
-      for (int i = 0; i < NV / 2; ++i) L[i] = NR_LOG2(e[i]);
+      for (int i = 0; i < NV / 2; ++i) L[i] = __builtin_amdgcn_logf(e[i]);
     } else if (st == 3) {
 #pragma unroll
-      for (int i = NV / 2; i < NV; ++i) L[i] = NR_LOG2(e[i]);
+      for (int i = NV / 2; i < NV; ++i) L[i] = __builtin_amdgcn_logf(e[i]);
       if constexpr (NABLA) {  // c = 2^-L = 1 / (1 + 2^t) for the slab codes (e no longer needed)
 #pragma unroll
         for (int i = 0; i < NV / 2; ++i) e[i] = __builtin_amdgcn_rcpf(e[i]);
@@ -1538,27 +1346,14 @@ struct FwdEpi4 {
 #pragma unroll
           for (int o = 0; o < 2; ++o) {
             const int i = (2 * q + o) * 4;
-#ifdef NR_SLAB32
-            pd.v[kNC * o + q] = code32(e[i], e[i + 1], e[i + 2], e[i + 3]);
-#else
             pd.v[kNC * o + q] = pack24(e[i], e[i + 1], e[i + 2], e[i + 3]);
-#endif
           }
       }
     } else if (st == 6) {
-#ifndef NR_EXP_NO_EPISPLIT  // timing experiment: next operand not written (results are garbage)
       split8a(make_float4(m[0], m[1], m[2], m[3]), make_float4(m[4], m[5], m[6], m[7]), sc[0] * kC, oh[0][c],
               ol[0][c]);
-#endif
     } else {
-#ifndef NR_EXP_NO_EPISPLIT
-      if constexpr (kNC == 2)
-        split8a(make_float4(m[8], m[9], m[10], m[11]), make_float4(m[12], m[13], m[14], m[15]), sc[1] * kC,
-                oh[kNC - 1][c], ol[kNC - 1][c]);
-#endif
-#ifndef NR_EXP_NO_ESTORE  // timing experiment: softplus' slab not written
-      if constexpr (NABLA) pend_chunk24(pd, sl, c, lane, NR_SLAB_NT);
-#endif
+      if constexpr (NABLA) pend_chunk24(pd, sl, c, lane, kSlabNT);
     }
   }
 };
@@ -1598,7 +1393,7 @@ struct F7Epi4 {
       }
     }
     if constexpr (NABLA)
-      if (st == 7) pend_chunk(pd, g7, 2 * c, lane, NR_FEAT_NT);
+      if (st == 7) pend_chunk(pd, g7, 2 * c, lane, kFeatNT);
   }
 };
 
@@ -1623,19 +1418,12 @@ struct BwdEpi4 {
       const int q = st >> 2, k = st & 3;
       if (q >= kNC) return;
       if (k < 2) {  // g * softplus'(z) = g - g 2^-L  (FwdEpi4's 24-bit codes of 2^-L)
-#ifdef NR_SLAB32
-        const float4 F = *(const float4*)((const char*)ws.slab_read() + ((kNC * k + q) * 64 + lane) * 16);
-        y[q][k] = code32_mul(F, zz.z[q][k]);
-#else
         const uint4 sw = *(const uint4*)((const char*)ws.slab_read() + ((kNC * k + q) * 64 + lane) * 16);
         y[q][k] = unpack24_mul(sw.x, sw.y, sw.z, zz.z[q][k]);
-#endif
       } else if (k == 2) {
         mrun[q] = amax8(mrun[q], y[q][0], y[q][1]);
       } else {
-#ifndef NR_EXP_NO_EPISPLIT
         split8a(y[q][0], y[q][1], sc[q], oh[q][c], ol[q][c]);
-#endif
         if (q == kNC - 1) ws.slab_consumed();
       }
     } else if (st == 7) {
@@ -1669,8 +1457,8 @@ void sdf4_kernel(SdfKArgs a) {
   constexpr int STAGE = STAGE_ == 3 ? 0 : (STAGE_ == 4 ? 2 : STAGE_);
   constexpr bool COMPACT = STAGE_ == 4;
   constexpr int NW = STAGE_ == 3 ? 4 : kW4;  // waves per workgroup
-  static_assert(STAGE_ != 3 || (!NABLA && !FEAT && kW4 == 8), "narrow tiles: forward-only launches");
-  static_assert(STAGE == 0 || (NABLA && !FEAT && kNC == 1), "deferred nablas: 16-point waves, no feature");
+  static_assert(STAGE_ != 3 || (!NABLA && !FEAT), "narrow tiles: forward-only launches");
+  static_assert(STAGE == 0 || (NABLA && !FEAT), "deferred nablas: no feature");
   constexpr int PPW = 16 * kNC * NW;  // points per workgroup tile
   constexpr int CB = chunk_bytes(18);  // largest SDF op chunk (F4: 14 + 4 input blocks)
   constexpr int C16 = chunk_bytes(16), C4 = chunk_bytes(4), C14 = chunk_bytes(14), C18 = chunk_bytes(18);
@@ -1678,7 +1466,7 @@ void sdf4_kernel(SdfKArgs a) {
   // launches (STAGE 1 included: its slabs go straight to HBM) stream through a 4-slot ring
   static_assert((size_t)kW4 * kNC * kSlabColBytes <= kScratchPerWG, "per-workgroup slab scratch");
   constexpr bool SLABS = NABLA && STAGE != 1;
-  constexpr int RING = SLABS ? 3 : NR_FWD_RING;
+  constexpr int RING = SLABS ? 3 : kFwdRing;
   __shared__ __attribute__((aligned(16))) char smem[RING * CB + (SLABS ? kSlabRing * kSlab4 : 0)];
   static_assert(RING * CB + (SLABS ? kSlabRing * kSlab4 : 0) <= 160 * 1024, "LDS budget");
   WStream4<CB, RING, NW> ws{smem, SLABS ? smem + RING * CB : nullptr, 0, 0, 0, 0};
@@ -1690,12 +1478,6 @@ void sdf4_kernel(SdfKArgs a) {
   auto OP = [&](int i) {  // ops packed back to back (nr_mlp.h)
     const char* w = W;
     asm volatile("" : "+s"(w));
-#ifdef NR_EXP_SHARED_W  // timing experiment: backward ops stream the forward ops' bytes (half the footprint)
-    if (i >= B7) {
-      constexpr int map[8] = {F1, F2, F3, F4, F5, F6, F7, F1};  // B7..B0
-      return w + sdf_op_off(map[i - B7]);
-    }
-#endif
     return w + sdf_op_off(i);
   };
   const float b8 = *(const float*)(W + a.L.misc_off);
@@ -1712,9 +1494,6 @@ void sdf4_kernel(SdfKArgs a) {
 #ifdef NR_EXP_STAMPS
   if ((threadIdx.x & 63) == 0)
     for (int i = 0; i < kStampPh; ++i) stamp_lds()[wave * kStampPh + i] = 0;
-#endif
-#ifdef NR_SDF4_PRIO  // static priority for the second-dispatched half (MI355X_MICROARCH.md, two waves per SIMD)
-  if (kWPE == 2 && wave >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
   if constexpr (STAGE == 2) ws.template start<C16, C16>(OP(B7), OP(B7) + C16);
   else if constexpr (RING == 4) ws.template start<C4, C4, C4>(OP(F0), OP(F0) + C4, OP(F0) + 2 * C4);
@@ -1932,7 +1711,7 @@ void sdf4_kernel(SdfKArgs a) {
           pd.o[2 * q] = r + (2 * c) * 4;
           pd.o[2 * q + 1] = r + (2 * c + 1) * 4;
         }
-        pd.put(fb, 2 * kNC, NR_FEAT_NT);
+        pd.put(fb, 2 * kNC, kFeatNT);
       };
       constexpr int NXT = NABLA ? C16 : C4;
       const char* n = NABLA ? OP(B7) : (has_next ? OP(F0) : nullptr);
@@ -3075,10 +2854,7 @@ void nerf4_kernel(NerfKArgs a) {
       op4<16, 16, C22, false, false>(ws, OP(N4), OP(N5), Uh, Ul, xinv, pd, nopre, ReluEpi4{Vh, Vl, sc, mrun}, lane);
 #pragma unroll
       for (int q = 0; q < kNC; ++q) {
-#ifdef NR_NERF4_KEEP_E
-        const float4* Eq = E[q];
-#else  // the embedding again from the point (no 24 registers held across N0..N4)
-        float4 Eq[6];
+        float4 Eq[6];  // the embedding again from the point (no 24 registers held across N0..N4)
         const float4 xin = *(const float4*)(a.x4 + pcq[q] * 4);
         const int gq = (int)opaque_lane(g);
 #pragma unroll
@@ -3089,7 +2865,6 @@ void nerf4_kernel(NerfKArgs a) {
                               nerf_embed4(f + 2, xin.x, xin.y, xin.z, xin.w),
                               nerf_embed4(f + 3, xin.x, xin.y, xin.z, xin.w));
         }
-#endif
 #pragma unroll
         for (int k = 0; k < 3; ++k) split8a(Eq[2 * k], Eq[2 * k + 1], sc[q], Vh[q][8 + k], Vl[q][8 + k]);
         mrun[q] = fmaxf(mrun[q], mE[q]);
@@ -3214,65 +2989,44 @@ __device__ __forceinline__ uint32_t tg_elem(bool blk, uint32_t p, uint32_t ld, u
   return blk ? (((p >> 4) * (ld >> 4) + (c >> 4)) << 8) + ((p & 15u) << 4) + (c & 15u) : p * ld + c;
 }
 
-// NR_TG_XPF: the next tile's input blocks are loaded during this tile's chunk loop (two per chunk, asm
+// Next-tile prefetch: the next tile's input blocks are loaded during this tile's chunk loop (kPer per chunk, asm
 // loads counted with the chunk's other VMEM), so a tile starts from registers instead of a chip-wide
 // load burst (tools/tg_driver.py --stamps: the tile start was 27-37 % of the wave time)
-#ifndef NR_TG_XPF
-#define NR_TG_XPF 1
-#endif
-#ifndef NR_TG_XPF_PER  // prefetched blocks issued per chunk iteration
-#define NR_TG_XPF_PER 2
-#endif
-#ifndef NR_TG_XPF_SPADJ  // blocks the adjoint GEMMs prefetch (their three epilogue tensors fill the registers)
-#define NR_TG_XPF_SPADJ 8
-#endif
-#ifndef NR_TG_RING  // weight-ring slots (4: three chunks in flight, ops of >= 4 chunks)
-#define NR_TG_RING 3
-#endif
-#ifndef NR_TG_DRAIN
-#define NR_TG_DRAIN 0
-#endif
-#ifndef NR_TG_COLD_WAIT  // load_seg's scalar path ends in a compiler-visible vmcnt(0) (see there)
-#define NR_TG_COLD_WAIT 1
-#endif
 template <int KB, int KB2, int NBO, int NB2, int MODE>
 __global__ __attribute__((amdgpu_flat_work_group_size(kT4, kT4), amdgpu_waves_per_eu(kWPE, kWPE)))
 void tgemm_kernel(TGemmArgs a) {
-  static_assert(kNC == 1, "tgemm_kernel: 16-point waves");
   constexpr int CB = chunk_bytes(KB);
   constexpr int NCH = NBO / 2, NS = KB / 2, KB1 = KB - KB2, NB1 = NBO - NB2;
   static_assert(NCH >= 2, "the 2-ahead stream needs >= 2 chunks");
   static_assert(NB1 % 2 == 0, "the output split falls between chunks");
-  constexpr int TRING = (NR_TG_RING == 4 && NCH >= 4 && 4 * CB <= 160 * 1024) ? 4 : 3;
+  constexpr int TRING = 3;       // weight-ring slots
   constexpr int LA = TRING - 1;  // chunks issued ahead of the one being computed
   using WS = WStream4<CB, TRING>;
   __shared__ __attribute__((aligned(16))) char smem[TRING * CB];
   WS ws{smem, nullptr, 0, 0, 0, 0};
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = lane & 15, g = lane >> 4;
-  if constexpr (TRING == 4)
-    ws.template start<CB, CB, CB>(uniform_ptr(a.op), uniform_ptr(a.op) + CB, uniform_ptr(a.op) + 2 * CB);
-  else
-    ws.template start<CB, CB>(uniform_ptr(a.op), uniform_ptr(a.op) + CB);
+  ws.template start<CB, CB>(uniform_ptr(a.op), uniform_ptr(a.op) + CB);
   // epilogue tensors by mode: TG_MUL / TG_RELUMASK read a; TG_SPADJ reads a (softplus'), g, zdot
   constexpr bool kA = MODE == TG_MUL || MODE == TG_SPADJ || MODE == TG_RELUMASK;
   constexpr bool kG = MODE == TG_SPADJ;
   constexpr int NA = kG ? 3 : (kA ? 1 : 0);
   // the g zdot term: g from a tensor, or the op's per-row vector (g_row: W8[0, :] for layer 7)
   const bool has_g = kG && (a.g != nullptr || a.g_row), g_tensor = kG && a.g != nullptr;
-#ifdef NR_EXP_STAMPS  // timing experiment: phases 0-3 of the chunk iterations as sdf4_kernel's, 4 = tile start
+#ifdef NR_EXP_STAMPS  // stamps build: phases 0-3 of the chunk iterations as sdf4_kernel's, 4 = tile start
   if (lane == 0)
     for (int i = 0; i < kStampPh; ++i) stamp_lds()[wave * kStampPh + i] = 0;
 #endif
   // next-tile prefetch: x1 blocks [0, NPF) (single-segment inputs; SPADJ holds 3 epilogue tensors in
   // registers and prefetches half)
-  constexpr int NPF = (NR_TG_XPF && KB2 == 0) ? ((MODE == TG_SPADJ ? NR_TG_XPF_SPADJ : (KB1 < 2 * NCH ? KB1 : 2 * NCH)) & ~1) : 0;
+  constexpr int kPer = 2;    // prefetched blocks issued per chunk iteration
+  constexpr int kSpAdj = 8;  // blocks the adjoint GEMMs prefetch (their three epilogue tensors fill the registers)
+  constexpr int NPF = KB2 == 0 ? ((MODE == TG_SPADJ ? kSpAdj : (KB1 < 2 * NCH ? KB1 : 2 * NCH)) & ~1) : 0;
   const bool blk1 = (a.blocked & NR_BLK_X1) != 0;
   const bool pf_ok = NPF > 0 && (blk1 || ((a.ld1 | (int64_t)((uintptr_t)a.x1 >> 2)) & 3) == 0);
   float4 Xn[NPF > 0 ? NPF : 1];
   bool have_pf = false;
   int nst_prev = 0;  // stores the previous tile's last flush issued (younger than its prefetch)
-  int rest_prev = 0;  // VMEM the previous chunk iteration issued after its epilogue-operand loads
   for (int64_t base = (int64_t)blockIdx.x * kPointsPerWG; base < a.P; base += (int64_t)gridDim.x * kPointsPerWG) {
     NR_STAMP(ts0);
     const bool has_next = base + (int64_t)gridDim.x * kPointsPerWG < a.P;
@@ -3314,17 +3068,14 @@ void tgemm_kernel(TGemmArgs a) {
             if (col + 1 < n) v.y = e[1];
             if (col + 2 < n) v.z = e[2];
             if (col + 3 < n) v.w = e[3];
-#if NR_TG_COLD_WAIT
             // a compiler-visible vmcnt(0) on this (partial-block / unaligned) path: otherwise its loads
             // stay "maybe in flight" where the paths merge, and the compiler drains every load and store
             // in flight at each tile start of every launch (the previous tile's stores included)
             __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
           }
           X[b0 + b] = v;
         }
       };
-#if NR_TG_COLD_WAIT
       if constexpr (NPF == KB1 && KB2 == 0) {
         // the prefetch covers every input block: the loads below run on the cold path only (the first
         // tile, or inputs the prefetch cannot take), which ends in its own compiler-visible vmcnt(0) --
@@ -3334,9 +3085,7 @@ void tgemm_kernel(TGemmArgs a) {
           load_seg(a.x1, a.ld1, a.n1, 0, KB1, blk1, 0);
           __builtin_amdgcn_s_waitcnt(0x0F70);
         }
-      } else
-#endif
-      {
+      } else {
         load_seg(a.x1, a.ld1, a.n1, 0, KB1, blk1, b_first);
         if constexpr (KB2 > 0) load_seg(a.x2, a.ld2, a.n2, KB1, KB2, (a.blocked & NR_BLK_X2) != 0);
       }
@@ -3414,7 +3163,6 @@ void tgemm_kernel(TGemmArgs a) {
       NR_STAMP(t0);
       int npend = 0;
       if (c + 1 < NCH) npend += aux_issue(c + 1, aux[(c + 1) & 1]);
-      const int naux = npend;  // what this iteration issues after its epilogue-operand loads
       if (c + LA < NCH) {
         ws.template issue<CB>(opc + (c + LA) * CB);
         npend += WS::template npieces<CB>();
@@ -3424,11 +3172,10 @@ void tgemm_kernel(TGemmArgs a) {
       }
       if (c > 0) npend += flush(c - 1);
       if constexpr (NPF > 0) {  // the next tile's x1 blocks 2c, 2c+1
-        constexpr int PER = NR_TG_XPF_PER;
-        if (pf_ok && has_next && PER * c < NPF) {
+        if (pf_ok && has_next && kPer * c < NPF) {
 #pragma unroll
-          for (int bb = 0; bb < PER; ++bb) {
-            const int b = PER * c + bb;
+          for (int bb = 0; bb < kPer; ++bb) {
+            const int b = kPer * c + bb;
             if (b < NPF) {
               Xn[b] = tg_load(a.x1, tg_elem(blk1, pcn, (uint32_t)a.ld1, (uint32_t)(16 * b + 4 * g)) * 4u);
               ++npend;
@@ -3451,11 +3198,8 @@ void tgemm_kernel(TGemmArgs a) {
         z[1] = fma4s(acc[0][1], inv, make_float4(0.f, 0.f, 0.f, 0.f));
       }
       // everything issued before this iteration has landed (this chunk's epilogue tensors, chunk c+1's
-      // weights); pinning keeps every use of the asm-loaded registers behind the wait.  With the 4-slot
-      // ring the previous iteration's weight DMA, stores and prefetch may still fly (issued after its
-      // epilogue-operand loads; chunk c+1's weights went out one iteration before that)
-      wait_vmcnt(npend + (TRING == 4 && c > 0 ? rest_prev : 0));
-      rest_prev = npend - naux;
+      // weights); pinning keeps every use of the asm-loaded registers behind the wait
+      wait_vmcnt(npend);
       NR_STAMP(t3);
       if constexpr (NA > 0) {
 #pragma unroll
@@ -3523,9 +3267,8 @@ void tgemm_kernel(TGemmArgs a) {
       NR_STAMP(t3e);
       // the counted wait above covered the next chunk's weights, so this iteration's DMA, stores and
       // prefetch stay in flight across the barrier (r05 with the prefetch: +0.8 % on the training step
-      // alternated; NR_TG_DRAIN=1 drains them here as r04 did; the 4-slot ring, NR_TG_RING=4, +0.7 %)
-      if constexpr (TRING == 3 && NR_TG_DRAIN) ws.flip(0);
-      else ws.flip_nowait();
+      // alternated, against draining them here; a 4-slot ring gave +0.7 %)
+      ws.flip_nowait();
 #ifdef NR_EXP_STAMPS
       const uint64_t t4 = stamp_now();
       stamp_add(0, t1 - t0);   // VMEM issue: epilogue operands, weight DMA, previous chunk's stores
@@ -3697,23 +3440,6 @@ __device__ __forceinline__ void pack_word(const PackOp& op, uint32_t* __restrict
     const int r = w & 3, lane = (w >> 2) & 63, t = w >> 8;
     const int b = t % KB, obl = t / KB;
     dst[e] = __float_as_uint(pack_src(op, 2 * c + obl, lane & 15, b, 4 * (lane >> 4) + r));
-  } else if (op.l32) {  // [s][hl][lane][8 halves], s = 16-feature k-step (nr_sdf5.hip): lane (r, h) element
-                        // el = W[row 32 c + r][16 s + 8 (el >> 2) + 4 h + (el & 3)]
-    const int q = w & 3, lane = (w >> 2) & 63, hl = (w >> 8) & 1, s = w >> 9;
-    const float sc = wscale(op);
-    const int row = lane & 31;
-    uint32_t word = 0;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int el = 2 * q + hh;
-      const int fi = 8 * (el >> 2) + 4 * (lane >> 5) + (el & 3);
-      const float v = pack_src(op, 2 * c + (row >> 4), row & 15, s, fi) * sc;
-      const _Float16 hi = (_Float16)v;
-      const _Float16 lo = (_Float16)(v - (float)hi);
-      const _Float16 out = hl ? lo : hi;
-      word |= (uint32_t)__builtin_bit_cast(uint16_t, out) << (16 * hh);
-    }
-    dst[e] = word;
   } else {  // [obl][s][hl][lane][8 halves]; word = halves (2q, 2q+1)
     const int q = w & 3, lane = (w >> 2) & 63, hl = (w >> 8) & 1, t = w >> 9;
     const int NS = KB / 2, s = t % NS, obl = t / NS;
@@ -3915,15 +3641,6 @@ int launch_pack_vec(const float* src, int off, int nvalid, int n, char* dst, hip
   return NR_OK;
 }
 
-int g_sdf5 = 0;
-// the 32x32x16 copy of the ops is laid out and packed only in processes started with NR_SDF5 set (a
-// process-wide constant, so every pack and launch of the process agrees on the layout): the experiment
-// costs nothing elsewhere (training repacks every optimizer step)
-const int g_sdf5_pack = [] {
-  const char* e = getenv("NR_SDF5");  // a nonzero integer (NR_SDF5=0 or empty: off, no second layout)
-  return (e && atoi(e) != 0) ? 1 : 0;
-}();
-
 static int cu_count() {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -3940,8 +3657,6 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
                float* feature, int nfreq, void* ws, size_t ws_bytes, hipStream_t stream, const int* P_dev,
                int P_mult) {
   if (P <= 0) return NR_OK;
-  if (g_sdf5 && !nabla && !feature && L.prec == NR_PREC_F16X3 && !L.siren && L.l32_off)
-    return launch_sdf5_fwd(L, packed, pts, P, sdf, nfreq, stream, P_dev, P_mult);
   const int grid = grid_for(P);
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, feature, (float4*)ws, nfreq, P_dev, P_mult, nullptr, nullptr,
              nullptr};
@@ -3973,7 +3688,7 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
   } else {
     if (L.prec == NR_PREC_F16X3) {
       if (feature) hipLaunchKernelGGL((sdf4_kernel<false, true, 0>), dim3(grid), dim3(kT4), 0, stream, a);
-      else if (kW4 == 8 && P <= (int64_t)64 * cu_count())  // a few thousand points: 64-point tiles on all CUs
+      else if (P <= (int64_t)64 * cu_count())  // a few thousand points: 64-point tiles on all CUs
         hipLaunchKernelGGL((sdf4_kernel<false, false, 3>), dim3(grid_for(P, 64)), dim3(256), 0, stream, a);
       else hipLaunchKernelGGL((sdf4_kernel<false, false, 0>), dim3(grid), dim3(kT4), 0, stream, a);
     }
@@ -3986,7 +3701,7 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
 int launch_sdf_deferred(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
                         int nfreq, float4* slabs, const int* tiles, const int* n_tiles, int stage, hipStream_t stream) {
   if (P <= 0) return NR_OK;
-  NR_REQUIRE(L.prec == NR_PREC_F16X3 && !L.siren && kNC == 1, NR_ERR_UNSUPPORTED, "deferred nablas: f16x3 softplus nets");
+  NR_REQUIRE(L.prec == NR_PREC_F16X3 && !L.siren, NR_ERR_UNSUPPORTED, "deferred nablas: f16x3 softplus nets");
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, nullptr, nullptr, nfreq, nullptr, 0, slabs, tiles, n_tiles};
   if (stage == 1) {
     ProfScope prof("sdf_nabla_fwd", (double)P, stream);
@@ -4116,7 +3831,7 @@ int launch_radiance(const RadLayout& L, const void* packed, const float* x, cons
 }  // namespace nr
 
 #ifdef NR_EXP_STAMPS
-// per-wave phase totals of the last sdf4_kernel launch (timing experiment builds only)
+// per-wave phase totals of the last sdf4_kernel launch (stamps builds only)
 extern "C" int nr_exp_stamps(unsigned long long* out, int n) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(nr::g_nr_stamps), sizeof(unsigned long long) * (size_t)n) == hipSuccess
              ? nr::kW4 * nr::kStampPh

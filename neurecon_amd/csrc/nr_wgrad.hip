@@ -35,19 +35,15 @@
 //    (k, i)'s ds_read_b32, B[k][j] likewise.  Each slice sums its rows in order, the slices are summed
 //    in fixed order: a deterministic fp32 reduction in place of hipBLASLt's split-K products.
 #include <algorithm>
-#include <cstdlib>
 #include "nr_common.h"
 
 namespace nr {
 
 constexpr int kWgThreads = 512;   // 8 waves: wave w owns output rows [32 w, 32 w + 32) of the m tile
 constexpr int kWgM = 256, kWgN = 128, kWgK = 32;
-#ifndef NR_WG_PP_BIT
-#define NR_WG_PP_BIT 0
-#endif
 // waves w with (w & bit) run the split before the MFMAs; 0 = none (measured r04: splitting the phases
 // between the two waves of a SIMD, bit 4, took 114 us per two-pair call against 104-107 without)
-constexpr int kPingPongBit = NR_WG_PP_BIT;
+constexpr int kPingPongBit = 0;
 constexpr int kAStride = 272;     // halfs per A row in LDS (544 B: 8 rows of a half-wave read land 8 banks apart)
 constexpr int kBStride = 144;     // halfs per B row (288 B, the same property)
 constexpr int kAPlane = kWgK * kAStride;
@@ -255,13 +251,6 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
   // no memory.  Issued unconditionally, so the compiler counts the loads in flight exactly (a
   // conditional prefetch makes it wait for all of them)
   auto load = [&](int ks, WgRegs& R, bool live) __attribute__((always_inline)) {
-#ifdef NR_WG_EXP_NO_LOAD
-    const float x = (float)(ks & 7) + 0.5f;
-    for (int j = 0; j < 4; ++j) R.va[j] = make_float4(x, x, x, x);
-    for (int j = 0; j < 2; ++j) { R.vb[j] = make_float4(x, x, x, x); R.vv[j] = x; }
-    R.q = 0;
-    return;
-#endif
     ks = live ? ks : 0;
     const int q = ks >= KP;
     const int64_t r0 = (int64_t)(ks - (q ? KP : 0)) * kWgK;
@@ -280,7 +269,6 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
     }
     R.q = q;
   };
-  [[maybe_unused]] float sink = 0.0f;  // timing experiments only (NR_WG_EXP_NO_STORE keeps the loads alive)
   // Running per-quad exponents: a quad keeps one scale over the slice (e only decreases), so MFMAs
   // accumulate straight into acc.  A k-step whose quad max M would reach 2^14 at the current scale
   // lowers it to put M at 2^(14 - kHeadroom) (16x headroom: later maxima rarely force another change),
@@ -290,10 +278,6 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
   int ea_cur = kExpCap, eb_cur = kExpCap;
   bool cha[2] = {false, false};
   auto store = [&](int stg, const WgRegs& R) __attribute__((always_inline)) {
-#ifdef NR_WG_EXP_NO_STORE
-    sink += R.va[0].x + R.va[1].y + R.va[2].z + R.va[3].w + R.vb[0].x + R.vb[1].w + R.vv[0] + R.vv[1];
-    return;
-#endif
     _Float16* S0 = lds + stg * kStage;
     if (want_cs && R.q == 0) cs = add4(cs, add4(add4(R.va[0], R.va[1]), add4(R.va[2], R.va[3])));
     if constexpr (VEC)
@@ -356,9 +340,6 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
   };
   auto compute = [&](int stg) __attribute__((always_inline)) {
     if (!wvalid) return;
-#ifdef NR_WG_EXP_NO_MFMA
-    return;
-#endif
     if constexpr (F32) {
       const float* A32 = (const float*)(lds + stg * kStage);
       const float* B32 = (const float*)(lds + stg * kStage + 2 * kAPlane);
@@ -412,7 +393,7 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
   __syncthreads();
   int ks = k0;
   // Within a barrier interval the MFMAs read stage stg and the split writes stage stg ^ 1, so their
-  // order is free (the kPingPongBit experiment: the two waves of a SIMD in different phases).
+  // order is free (kPingPongBit: the two waves of a SIMD in different phases).
   const bool split_first = (w & kPingPongBit) != 0;
   auto step = [&](int stg, WgRegs& refill, WgRegs& next) __attribute__((always_inline)) {
     load(ks + 3, refill, ks + 3 < k1);
@@ -439,9 +420,7 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
     if (lane < 8) s_rat[2][ac >> 2] = __builtin_ldexpf(1.0f, -ea_cur);
     if (lane < 4) s_rat[2][64 + (bc >> 2)] = __builtin_ldexpf(1.0f, -eb_cur);
     __syncthreads();
-#ifndef NR_WG_EXP_NO_MFMA
     if (wvalid) rescale(2);
-#endif
   }
 
   // partial tile: lane (G, col) register r holds row 4G + r of each 16 x 16 tile -> part[s][n][m]
@@ -453,9 +432,6 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(WgKArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int64_t nn = n0 + 16 * j + col, mm = m0 + 32 * w + 16 * i + 4 * G;
-#ifdef NR_WG_EXP_NO_STORE
-        acc[i][j][0] += sink;
-#endif
         *(float4*)(P0 + nn * ldp + mm) = wvalid ? make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3])
                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
       }
@@ -611,12 +587,6 @@ int nr_wgrad(const NrWgrad* w, void* stream) {
     NR_REQUIRE(ok, NR_ERR_ARG, "nr_wgrad: a blocked operand needs P and its leading dimension multiples of 16");
   }
   WgPlan p = wgrad_plan(w->P, w->m, w->n, w->npairs);
-#ifdef NR_WG_EXP_SLICES_ENV  // measurement builds only (tools/wgrad_bench.py): fewer slices
-  if (const char* e = getenv("NR_WGRAD_SLICES")) {
-    const int s = atoi(e);
-    if (s > 0 && s < p.S) p.S = s;
-  }
-#endif
   NR_REQUIRE(w->workspace && w->workspace_bytes >= p.part_bytes + p.cs_bytes + p.vec_bytes, NR_ERR_WORKSPACE,
              "nr_wgrad: workspace too small (nr_wgrad_workspace_bytes)");
   hipStream_t st = (hipStream_t)stream;

@@ -218,14 +218,9 @@ def test_train_gemm_rejects_bad_arguments(lib):
     assert call(args(P=0))[0] == 0                                                             # empty: no launch
 
 
-def _lib_env_int(name):
-    from neurecon_amd import _lib
-    return _lib._env_int(name)
-
-
 def test_r06_entries_reject_bad_arguments(lib):
     """nr_gemm32 checks its sizes and leading dimensions before any HIP call (fake device pointers);
-    nr_sdf5_enable refuses without NR_SDF5 at load (the packs would lack the 32x32x16 layout)"""
+    the library no longer exports the removed nr_sdf5_enable switch"""
     A, B, C = 0x1000, 0x2000, 0x3000
     assert lib.nr_gemm32(None, 8, B, 8, 0, None, C, 8, 16, 8, 8, 0, None) == -1
     assert 'null argument' in lib.nr_last_error().decode()
@@ -238,9 +233,7 @@ def test_r06_entries_reject_bad_arguments(lib):
     assert lib.nr_gemm32(A, 8, B, 8, 0, None, C, 8, 128 * 65536, 8, 8, 0, None) == -1
     assert 'row tiles' in lib.nr_last_error().decode()
     assert lib.nr_gemm32(A, 8, B, 8, 0, None, C, 8, 0, 8, 8, 0, None) == 0        # empty: no launch
-    if not _lib_env_int('NR_SDF5'):
-        assert lib.nr_sdf5_enable(1) == -1 and 'NR_SDF5' in lib.nr_last_error().decode()
-        assert lib.nr_sdf5_enable(0) == 0
+    assert not hasattr(lib, 'nr_sdf5_enable')
 
 
 def test_adam_step_rejects_bad_arguments(lib):

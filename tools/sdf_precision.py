@@ -1,6 +1,6 @@
 """SDF / nabla error of the HIP SDF kernel (fp32 and f16x3) against the oracle network evaluated in
 float64, on uniform points in [-1, 1]^3 and on points within 0.05 of the zero level set.
-Run on a GPU box; NR_LIB selects the library (tools/build_variants.py experiments)."""
+Run on a GPU box; NR_LIB selects the library."""
 import os
 import sys
 

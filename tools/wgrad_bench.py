@@ -1,7 +1,6 @@
 """nr_wgrad timing on the training step's main shape (P = 65536, 256 x 256, one and two pairs) vs the
 split-K hipBLASLt product it replaces; run under rocprofv3 --kernel-trace --stats to split the
-kernel from its reduction.  NR_WGRAD_SLICES=<S> overrides the slice count (fewer, larger slices) in the wg_slices_env variant build
-(tools/build_variants.py; NR_LIB=neurecon_amd/_exp/libnrhip_wg_slices_env.so)."""
+kernel from its reduction."""
 import os
 import sys
 import time
@@ -47,8 +46,8 @@ def main():
             continue
         us = t(fn)
         npairs = 2 if '2' in name else 1
-        print(f'P={P}{" blocked" if blk else ""} {name}: {us:.1f} us, {npairs * 2 * P * 256 * 4 / us / 1e6:.2f} TB/s of operands '
-              f'(NR_WGRAD_SLICES={os.environ.get("NR_WGRAD_SLICES", "-")})', flush=True)
+        print(f'P={P}{" blocked" if blk else ""} {name}: {us:.1f} us, {npairs * 2 * P * 256 * 4 / us / 1e6:.2f} TB/s of operands',
+              flush=True)
 
 
 if __name__ == '__main__':
