@@ -225,6 +225,10 @@ typedef struct {
    * max_workspace_bytes (0: NR_DEFAULT_WORKSPACE_BYTES), down to one 16-ray chunk. */
   int64_t max_chunk_rays;
   size_t max_workspace_bytes;
+  /* Optional fold pack (nr_neus_fold_pack) of the same two nets: the mid-point SDF launch then writes
+   * u = (W0f W8f) h7 + (W0f b8f + b0) in the geometry feature's place and the radiance net's layer 0
+   * runs over its small inputs only.  NULL: the feature goes through layer 0 as in the reference. */
+  const void* fold_packed;
 } NrNeusArgs;
 
 #define NR_DEFAULT_WORKSPACE_BYTES ((size_t)4 << 30) /* 4 GiB */
@@ -232,6 +236,23 @@ typedef struct {
 
 size_t nr_neus_workspace_bytes(const NrNeusArgs* a);
 int nr_neus_render(const NrNeusArgs* a, void* stream);
+
+/* Fold of the SDF net's geometry-feature layer into the radiance net's layer 0.  The feature
+ * f = W8[1:] h7 + b8[1:] has no activation (base.py:255-256) and layer 0 is a Linear over
+ * cat([x, embed_view(v), n, f]) (base.py:382), so W0f f = (W0f W8[1:]) h7 + W0f b8[1:] with W0f the
+ * feature columns of W0.  nr_neus_fold_pack takes the two layers' effective fp32 weights as nr_sdf_pack
+ * and nr_radiance_pack do (W8 [257, 256], b8 [257], W0 [256, n_small + 256], b0 [256]; device pointers),
+ * forms the products (exact fp32 products, fp64 sums, one rounding) and packs them.
+ * nr_neus_fold_packed_bytes is 0 where the fold does not apply: it needs both nets in f16x3, the
+ * softplus SDF net and a ReLU D = 4 radiance net.  Re-pack whenever either net's weights change. */
+size_t nr_neus_fold_packed_bytes(const NrSdfDesc* sdf, const NrRadDesc* rad);
+int nr_neus_fold_pack(const NrSdfDesc* sdf, const NrRadDesc* rad, const float* W8, const float* b8, const float* W0,
+                      const float* b0, void* packed, void* stream);
+/* The folded pair on a point list: pts [P,3], view dirs vdir[(p / vdir_div) * 3 + c], normals [P,3]
+ * -> rgb [P,3].  u [P,256] and sdf [P] are caller scratch (the folded SDF launch's outputs). */
+int nr_neus_fold_forward(const NrSdfDesc* sdf, const void* sdf_packed, const NrRadDesc* rad, const void* rad_packed,
+                         const void* fold_packed, const float* pts, const float* vdir, int64_t vdir_div,
+                         const float* normals, int64_t P, float* u, float* sdf_out, float* rgb, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * VolSDF rendering (models/frameworks/volsdf.py:377-551, render mode: perturb=False, builtin

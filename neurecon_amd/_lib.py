@@ -57,6 +57,7 @@ class NrNeusArgs(ctypes.Structure):
         ('workspace', _c_p), ('workspace_bytes', _c_sz),
         ('u_rand', _c_p), ('t_out_rand', _c_p), ('s_dev', _c_p), ('sample_only', _c_i), ('d_all_out', _c_p),
         ('no_mid_skip', _c_i), ('no_defer', _c_i), ('max_chunk_rays', _c_i64), ('max_workspace_bytes', _c_sz),
+        ('fold_packed', _c_p),
     ]
 
 
@@ -176,6 +177,11 @@ _SIGS = {
                                    _c_i64, _c_p, _c_p, _c_p, ctypes.POINTER(_c_p), _c_p]),
     'nr_neus_workspace_bytes': (_c_sz, [ctypes.POINTER(NrNeusArgs)]),
     'nr_neus_render': (_c_i, [ctypes.POINTER(NrNeusArgs), _c_p]),
+    'nr_neus_fold_packed_bytes': (_c_sz, [ctypes.POINTER(NrSdfDesc), ctypes.POINTER(NrRadDesc)]),
+    'nr_neus_fold_pack': (_c_i, [ctypes.POINTER(NrSdfDesc), ctypes.POINTER(NrRadDesc), _c_p, _c_p, _c_p, _c_p, _c_p,
+                                 _c_p]),
+    'nr_neus_fold_forward': (_c_i, [ctypes.POINTER(NrSdfDesc), _c_p, ctypes.POINTER(NrRadDesc), _c_p, _c_p, _c_p, _c_p,
+                                    _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
     'nr_volsdf_workspace_bytes': (_c_sz, [ctypes.POINTER(NrVolsdfArgs)]),
     'nr_volsdf_render': (_c_i, [ctypes.POINTER(NrVolsdfArgs), _c_p]),
     'nr_unisurf_workspace_bytes': (_c_sz, [ctypes.POINTER(NrUnisurfArgs)]),

@@ -364,6 +364,29 @@ class RadianceNet(nn.Module):
         self._nr_cache = (key, desc, packed, Ws, bs)
         return desc, packed
 
+    def nr_fold_packed(self, implicit_surface, device):
+        """NeuS render fold pack (nr_neus_fold_pack): the SDF net's geometry-feature layer (base.py:255-256,
+        no activation) folded into this net's layer 0 (base.py:382), or None where the fold does not apply
+        (fp32 or SIREN nets, D != 4).  Cached on this net; the key is both nets' pack versions, so the
+        fold is re-packed whenever either net's pack is."""
+        sdf_desc, _ = implicit_surface.nr_packed(device)
+        rad_desc, _ = self.nr_packed(device)
+        key = (implicit_surface._nr_cache[0], self._nr_cache[0])
+        cache = self.__dict__.get('_nr_fold_cache')
+        if cache is not None and cache[0] == key:
+            return cache[1]
+        lib = L.lib()
+        nbytes = lib.nr_neus_fold_packed_bytes(ctypes.byref(sdf_desc), ctypes.byref(rad_desc))
+        packed = None
+        if nbytes:
+            sW, sb = implicit_surface._nr_cache[3], implicit_surface._nr_cache[4]  # effective weights on `device`
+            rW, rb = self._nr_cache[3], self._nr_cache[4]
+            packed = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            L.check(lib.nr_neus_fold_pack(ctypes.byref(sdf_desc), ctypes.byref(rad_desc), L.ptr(sW[-1]), L.ptr(sb[-1]),
+                                          L.ptr(rW[0]), L.ptr(rb[0]), L.ptr(packed), L.stream_of(device)))
+        self.__dict__['_nr_fold_cache'] = (key, packed)
+        return packed
+
     def forward(self, x, view_dirs, normals, geometry_feature):
         """base.py:372-391 (render mode; with a graph when training)."""
         L.require_gpu(x, 'points')

@@ -110,6 +110,29 @@ RadLayout rad_layout(const NrRadDesc& d) {
   return L;
 }
 
+bool fold_applies(const NrSdfDesc& sd, const NrRadDesc& rd) {
+  return sd.precision == NR_PREC_F16X3 && !sd.siren && sd.W_geo_feat == 256 && rd.precision == NR_PREC_F16X3 &&
+         !rd.siren && rd.D == 4 && rd.W_geo_feat == 256;
+}
+
+FoldLayout fold_layout(const RadLayout& RL) {
+  FoldLayout F{};
+  F.kbs = RL.kbs;
+  size_t off = 0;
+  F.f8_off = (uint32_t)off;
+  off += 8 * (size_t)chunk_bytes_host(16);
+  F.r0_off = (uint32_t)off;
+  off += 8 * (size_t)chunk_bytes_host(RL.kbs);
+  F.scale_off = (uint32_t)off;
+  off = align256(off + 2 * 4);
+  F.bound_off = (uint32_t)off;
+  off = align256(off + 2 * 2 * 4);
+  F.u_off = (uint32_t)off;
+  off = align256(off + (256 * 256 + 256) * 4);
+  F.total = (uint32_t)off;
+  return F;
+}
+
 int check_nerf_desc(const NrNerfDesc* d) {
   NR_REQUIRE(d, NR_ERR_ARG, "null NrNerfDesc");
   NR_REQUIRE(d->D == 8 && d->W == 256 && d->skip == 4 && d->input_ch == 4 && d->multires == 10 &&
@@ -332,12 +355,20 @@ static int neus_chunk(const NrNeusArgs& a, const NeusPlan& pl, int64_t ray0, int
     return rc;
   // SDF + nablas + geometry feature at the mid-points, then the radiance net (neus.py:103-106, :298)
   const int64_t Pm = (int64_t)(c.S - 1) * R;
+  // with a fold pack, feat_m carries u (F8' in F8's place) and the radiance net's layer 0 is R0'
+  const char* f8p = nullptr;
+  const char* r0p = nullptr;
+  if (a.fold_packed) {
+    const FoldLayout FL = fold_layout(RL);
+    f8p = (const char*)a.fold_packed + FL.f8_off;
+    r0p = (const char*)a.fold_packed + FL.r0_off;
+  }
   if (a.radiance_out || a.no_mid_skip) {  // every mid-point, as the reference
     if ((rc = launch_sdf(SL, a.sdf_packed, c.mids, Pm, c.sdf_m, c.nab_m, c.feat_m, a.sdf->multires, mlp_ws, mlp_bytes,
-                         st)))
+                         st, nullptr, 0, f8p)))
       return rc;
     if ((rc = launch_radiance(RL, a.rad_packed, c.mids, c.rd, 1, R, c.nab_m, c.feat_m, Pm, c.rad_m,
-                              a.rad->multires_view, st)))
+                              a.rad->multires_view, st, nullptr, r0p)))
       return rc;
   } else {  // only the mid-points whose alpha is not exactly 0 (neus_mid_compact); bit-identical maps
     char* wsb = (char*)a.workspace;
@@ -352,10 +383,10 @@ static int neus_chunk(const NrNeusArgs& a, const NeusPlan& pl, int64_t ray0, int
                        slot, midc, vdc);
     NR_HIP_CHECK(hipGetLastError());
     if ((rc = launch_sdf(SL, a.sdf_packed, midc, Pm, c.sdf_m, c.nab_m, c.feat_m, a.sdf->multires, mlp_ws, mlp_bytes,
-                         st, cnt, 1)))
+                         st, cnt, 1, f8p)))
       return rc;
     if ((rc = launch_radiance(RL, a.rad_packed, midc, vdc, 1, INT64_MAX, c.nab_m, c.feat_m, Pm, radc,
-                              a.rad->multires_view, st, cnt)))
+                              a.rad->multires_view, st, cnt, r0p)))
       return rc;
     hipLaunchKernelGGL(neus_mid_scatter, g1, dim3(256), 0, st, slot, radc, Pm, c.rad_m);
     NR_HIP_CHECK(hipGetLastError());
@@ -1168,6 +1199,8 @@ int nr_neus_render(const NrNeusArgs* a, void* stream) {
              NR_ERR_ARG, "nr_neus_render: null ray or output pointer");
   NR_REQUIRE(a->sdf_packed && a->rad && (a->rad_packed || a->sample_only) && a->t_coarse, NR_ERR_ARG,
              "nr_neus_render: null argument");
+  NR_REQUIRE(!a->fold_packed || fold_applies(*a->sdf, *a->rad), NR_ERR_ARG,
+             "nr_neus_render: a fold pack needs the f16x3 softplus SDF net and a f16x3 ReLU D=4 radiance net");
   NR_REQUIRE(a->N_samples >= 2, NR_ERR_ARG, "nr_neus_render: N_samples must be >= 2");
   NR_REQUIRE(a->n_rays <= 0 || a->sample_only || !a->calc_normal || a->normals, NR_ERR_ARG,
              "nr_neus_render: calc_normal needs normals output");
@@ -1207,6 +1240,66 @@ int nr_neus_render(const NrNeusArgs* a, void* stream) {
     if ((rc = neus_chunk(*a, pl, r0, R, (hipStream_t)stream))) return rc;
   }
   return NR_OK;
+}
+
+// Fold of the geometry-feature layer (base.py:255-256: no activation) into the radiance net's layer 0
+// (base.py:382: a Linear over cat([x, embed_view(v), n, feature])): U = W0f W8[1:], bu = W0f b8[1:] + b0
+static int check_fold(const NrSdfDesc* sd, const NrRadDesc* rd) {
+  int rc = check_sdf_desc(sd);
+  if (rc) return rc;
+  if ((rc = check_rad_desc(rd))) return rc;
+  NR_REQUIRE(fold_applies(*sd, *rd), NR_ERR_UNSUPPORTED,
+             "NeuS fold: needs the f16x3 softplus SDF net and a f16x3 ReLU D=4 radiance net");
+  return NR_OK;
+}
+
+size_t nr_neus_fold_packed_bytes(const NrSdfDesc* sd, const NrRadDesc* rd) {
+  if (!sd || !rd || check_sdf_desc(sd) || check_rad_desc(rd) || !fold_applies(*sd, *rd)) return 0;
+  return fold_layout(rad_layout(*rd)).total;
+}
+
+int nr_neus_fold_pack(const NrSdfDesc* sd, const NrRadDesc* rd, const float* W8, const float* b8, const float* W0,
+                      const float* b0, void* packed, void* stream) {
+  int rc = check_fold(sd, rd);
+  if (rc) return rc;
+  NR_REQUIRE(W8 && b8 && W0 && b0 && packed, NR_ERR_ARG, "nr_neus_fold_pack: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const RadLayout RL = rad_layout(*rd);
+  const FoldLayout F = fold_layout(RL);
+  char* P = (char*)packed;
+  const int ns = RL.n_small, ld0 = ns + 256;
+  float* U = (float*)(P + F.u_off);
+  float* bu = U + 256 * 256;
+  // exact fp32 products, fp64 sums, one rounding (nr_gemm32's default mode); b0 added last
+  if ((rc = nr_gemm32(W0 + ns, ld0, W8 + 256, 256, 0, nullptr, U, 256, 256, 256, 256, 0, stream))) return rc;
+  if ((rc = nr_gemm32(b8 + 1, 256, W0 + ns, ld0, 1, b0, bu, 256, 1, 256, 256, 0, stream))) return rc;
+  float* wmax = (float*)(P + F.scale_off);
+  float* bound = (float*)(P + F.bound_off);
+  PackOp ops[2];
+  ops[0] = mkop(U, bu, 256, 256, 0, seg(16, 0, 256), none(), seg(16, 0, 256), none(), 1.0f, NR_PREC_F16X3, wmax);
+  ops[1] = mkop(W0, nullptr, 256, ld0, 0, seg(16, 0, 256), none(), seg(RL.kbs, 0, ns), none(), 1.0f, NR_PREC_F16X3,
+                wmax + 1);
+  char* dst[2] = {P + F.f8_off, P + F.r0_off};
+  for (int i = 0; i < 2; ++i) ops[i].bound = bound + 2 * i;
+  return launch_pack_ops(ops, dst, 2, st);
+}
+
+int nr_neus_fold_forward(const NrSdfDesc* sd, const void* sdf_packed, const NrRadDesc* rd, const void* rad_packed,
+                         const void* fold_packed, const float* pts, const float* vdir, int64_t vdir_div,
+                         const float* normals, int64_t P, float* u, float* sdf_out, float* rgb, void* stream) {
+  int rc = check_fold(sd, rd);
+  if (rc) return rc;
+  NR_REQUIRE(sdf_packed && rad_packed && fold_packed && pts && (rd->no_view_dirs || (vdir && normals)) && u &&
+                 sdf_out && rgb && vdir_div > 0 && P >= 0,
+             NR_ERR_ARG, "nr_neus_fold_forward: bad argument");
+  const RadLayout RL = rad_layout(*rd);
+  const FoldLayout F = fold_layout(RL);
+  const char* fp = (const char*)fold_packed;
+  if ((rc = launch_sdf(sdf_layout(*sd), sdf_packed, pts, P, sdf_out, nullptr, u, sd->multires, nullptr, 0,
+                       (hipStream_t)stream, nullptr, 0, fp + F.f8_off)))
+    return rc;
+  return launch_radiance(RL, rad_packed, pts, vdir, vdir_div, INT64_MAX, normals, u, P, rgb, rd->multires_view,
+                         (hipStream_t)stream, nullptr, fp + F.r0_off);
 }
 
 size_t nr_volsdf_workspace_bytes(const NrVolsdfArgs* a) {

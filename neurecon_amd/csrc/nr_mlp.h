@@ -128,7 +128,8 @@ int launch_pack_ops(const PackOp* ops, char* const* dst, int nops, hipStream_t s
 int launch_pack_vec(const float* src, int off, int nvalid, int n, char* dst, hipStream_t stream);
 int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
                float* feature, int nfreq, void* ws, size_t ws_bytes, hipStream_t stream,
-               const int* P_dev = nullptr, int P_mult = 0);  // P_dev: device count, P_eff = min(P, *P_dev * P_mult)
+               const int* P_dev = nullptr, int P_mult = 0,  // P_dev: device count, P_eff = min(P, *P_dev * P_mult)
+               const void* f8_alt = nullptr);  // f16x3 softplus net: a packed op run in F8's place (fold_layout's F8')
 // deferred sample nablas (sdf4_kernel STAGE 1 / 2): stage 1 = sdf + slabs per 16-point tile into
 // `slabs` (P/16 x kSlabColBytes); stage 2 = nablas of the tiles tiles[0 .. *n_tiles) from their slabs;
 // stage 4 = nablas of the points tiles[0 .. *n_tiles) (neus_point_list's layout: 16-aligned segments of
@@ -140,7 +141,23 @@ int launch_nerf(const NerfLayout& L, const void* packed, const float* x4, const 
                 const int* P_dev = nullptr);  // P_dev: device count, P_eff = min(P, *P_dev)
 int launch_radiance(const RadLayout& L, const void* packed, const float* x, const float* vdir, int64_t vdiv,
                     int64_t vmod, const float* normals, const float* feature, int64_t P, float* rgb, int nfreq_view,
-                    hipStream_t stream, const int* P_dev = nullptr);  // P_dev: device count, P_eff = min(P, *P_dev)
+                    hipStream_t stream, const int* P_dev = nullptr,  // P_dev: device count, P_eff = min(P, *P_dev)
+                    const void* r0_fold = nullptr);  // rad4_kernel case: `feature` holds u, layer 0 runs fold_layout's R0'
+
+// NeuS fold pack (nr_neus_fold_pack): the SDF net's feature layer folded into the radiance net's
+// layer 0.  F8' (KB 16, NBO 16: h7 -> u = U h7 + bu) runs in F8's place in sdf4_kernel; R0' (KB kbs,
+// NBO 16: the small inputs' columns of layer 0, zero bias) is rad4_kernel's op 0, u added in its epilogue.
+struct FoldLayout {
+  uint32_t f8_off, r0_off;
+  uint32_t scale_off;  // [2] max |W| per op
+  uint32_t bound_off;  // [2][2] max row L1 norm, max |bias| per op
+  uint32_t u_off;      // pack-time scratch: U [256][256] fp32, then bu [256]
+  uint32_t total;
+  int kbs;
+};
+FoldLayout fold_layout(const RadLayout& RL);
+// the fold applies: f16x3 softplus SDF net, f16x3 ReLU D = 4 radiance net (rad4_kernel)
+bool fold_applies(const NrSdfDesc& sd, const NrRadDesc& rd);
 
 // training forward of a ReLU D=4 radiance net on its fp32 pack: h[0..3] [P][256], rgb [P][3]
 int launch_radiance_train32(const RadLayout& L, const void* packed, const float* feat, const float* small,

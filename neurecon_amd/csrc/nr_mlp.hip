@@ -581,6 +581,7 @@ struct SdfKArgs {
   float4* slabs;      // deferred nablas: per 16-point tile of the launch, kSlabColBytes (nr_mlp.h layout)
   const int* tiles;   // STAGE 2: 16-point tiles to run the reverse pass on
   const int* n_tiles; //   ... and their count (device)
+  const char* f8_alt; // sdf4_kernel: a packed op to run in F8's place (the NeuS fold's F8', nr_neus_fold_pack), or null
 };
 
 template <int P, bool NABLA>
@@ -1480,6 +1481,12 @@ void sdf4_kernel(SdfKArgs a) {
     asm volatile("" : "+s"(w));
     return w + sdf_op_off(i);
   };
+  // F8, or the op the launch runs in its place (same shape: KB 16, NBO 16)
+  auto OPF8 = [&]() {
+    const char* w = a.f8_alt;
+    asm volatile("" : "+s"(w));
+    return w ? w : OP(F8);
+  };
   const float b8 = *(const float*)(W + a.L.misc_off);
   // this wave's slabs: [layer 8][block 16][column kNC][lane 64] float4 (128 KB per column); the
   // deferred stages keep them per 16-point tile of the launch (set per tile below)
@@ -1684,7 +1691,9 @@ void sdf4_kernel(SdfKArgs a) {
       next_scales(16, kSpSlack, zero2, sc);
       F7Epi4<NABLA, FEAT> epi{Uh, Ul, sc, slab(7), mrun, sdf_part, pd, lane};
       constexpr int NXT = ((NABLA && STAGE == 0) || FEAT) ? C16 : C4;
-      const char* n = FEAT ? OP(F8) : ((NABLA && STAGE == 0) ? OP(B7) : (has_next ? OP(F0) : nullptr));
+      const char* n;
+      if constexpr (FEAT) n = OPF8();
+      else n = (NABLA && STAGE == 0) ? OP(B7) : (has_next ? OP(F0) : nullptr);
       op4<16, 16, NXT, true, false>(ws, OP(F7), n, Vh, Vl, xinv, pd, nopre, epi, lane);
       finish(sc);
     }
@@ -1715,7 +1724,7 @@ void sdf4_kernel(SdfKArgs a) {
       };
       constexpr int NXT = NABLA ? C16 : C4;
       const char* n = NABLA ? OP(B7) : (has_next ? OP(F0) : nullptr);
-      op4<16, 16, NXT, false, false>(ws, OP(F8), n, Uh, Ul, xinv, pd, nopre, epi, lane);
+      op4<16, 16, NXT, false, false>(ws, OPF8(), n, Uh, Ul, xinv, pd, nopre, epi, lane);
     }
     }  // STAGE != 2: forward
     if constexpr (NABLA && STAGE == 1) {  // the slabs stay for the reverse-pass launch
@@ -1941,6 +1950,7 @@ struct RadKArgs {
   float* rgb;
   int nfreq_view;  // <0: identity
   const int* P_dev;  // optional device count: the first min(P, *P_dev) points are evaluated
+  const char* r0_fold;  // rad4_kernel<KBS, true>: the fold pack's R0' (then `feature` holds u), or null
 };
 
 // small input features [x(3), view-embedding(3+6F or 3), normals(3)] in block layout ([x(3)] only
@@ -2200,23 +2210,50 @@ struct HeadEpi4 {
   }
 };
 
-template <int KBS>
+// FOLD (NeuS render, nr_neus_fold_pack): a.feature holds u = (W0f W8f) h7 + (W0f b8f + b0), the
+// geometry feature's share of layer 0 with its bias, written by sdf4_kernel's F8'.  Op 0 is R0'
+// (a.r0_fold) over the small inputs alone, and u, kept in fp32 registers, is added in its epilogue.
+struct FoldEpi4 {
+  f16x8 (&oh)[kNC][12];
+  f16x8 (&ol)[kNC][12];
+  const float (&sc)[kNC];
+  float (&mrun)[kNC];
+  const float4 (&u)[kNC][16];
+  float4 y[kNC][2];
+  __device__ __forceinline__ void operator()(int c, const Z4& zz, int st) {
+    const int q = st >> 2, k = st & 3;
+    if (q >= kNC) return;
+    if (k < 2) {
+      const float4 z = zz.z[q][k], v = u[q][2 * c + k];
+      y[q][k] = make_float4(fmaxf(z.x + v.x, 0.0f), fmaxf(z.y + v.y, 0.0f), fmaxf(z.z + v.z, 0.0f),
+                            fmaxf(z.w + v.w, 0.0f));
+    } else if (k == 2) {
+      mrun[q] = amax8(mrun[q], y[q][0], y[q][1]);
+    } else {
+      split8a(y[q][0], y[q][1], sc[q], oh[q][c], ol[q][c]);
+    }
+  }
+};
+
+template <int KBS, bool FOLD>
 __global__ __attribute__((amdgpu_flat_work_group_size(kT4, kT4), amdgpu_waves_per_eu(kWPE, kWPE)))
 void rad4_kernel(RadKArgs a) {
-  constexpr int K0 = 16 + KBS;  // op 0's input blocks: feature (16), then the small inputs
+  constexpr int KF = FOLD ? 0 : 16;  // op 0's input blocks: feature (16 unless folded), then the small inputs
+  constexpr int K0 = KF + KBS;
   constexpr int C0 = chunk_bytes(K0), C16 = chunk_bytes(16);
-  __shared__ __attribute__((aligned(16))) char smem[kRing * C0 + (3 * 256 + 4) * 4];
-  static_assert(kRing * C0 + (3 * 256 + 4) * 4 <= 160 * 1024, "LDS budget");
-  WStream4<C0> ws{smem, nullptr, 0, 0, 0};
-  float* head = (float*)(smem + kRing * C0);  // [3][256] weights, then [3] bias
+  constexpr int CM = C0 > C16 ? C0 : C16;  // the ring's slot
+  __shared__ __attribute__((aligned(16))) char smem[kRing * CM + (3 * 256 + 4) * 4];
+  static_assert(kRing * CM + (3 * 256 + 4) * 4 <= 160 * 1024, "LDS budget");
+  WStream4<CM> ws{smem, nullptr, 0, 0, 0};
+  float* head = (float*)(smem + kRing * CM);  // [3][256] weights, then [3] bias
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = lane & 15, g = lane >> 4;
   const RadLayout& L = a.L;
   const char* W = a.packed;
   auto OP = [&](int i) {
-    const char* w = W;
+    const char* w = FOLD && i == 0 ? a.r0_fold : W;
     asm volatile("" : "+s"(w));
-    return w + L.op_off[i];
+    return FOLD && i == 0 ? w : w + L.op_off[i];
   };
   const bool view = L.view != 0;
   {
@@ -2232,6 +2269,8 @@ void rad4_kernel(RadKArgs a) {
     const int64_t p0 = base + wave * 16 * kNC;
     f16x8 Uh[kNC][12], Ul[kNC][12], Vh[kNC][12], Vl[kNC][12];
     float m_in[kNC], xinv[kNC], mrun[kNC];
+    float4 ufold[kNC][FOLD ? 16 : 1];  // FOLD: the point's u, rows 16 b + 4 g .. + 3 (the accumulator layout)
+    float umax[kNC];                   // ... and its max |u| over the point's 256 rows
     bool valid[kNC];
 #pragma unroll
     for (int q = 0; q < kNC; ++q) {
@@ -2249,21 +2288,31 @@ void rad4_kernel(RadKArgs a) {
         }
       }
       // the small inputs first: their embedding calls then see few live registers
-      float4 X[16 + KBS];
+      float4 X[K0];
       const int gq = (int)opaque_lane(g);  // not hoistable: the 4 KBS feature indices' tests stay in the tile
 #pragma unroll
       for (int b = 0; b < KBS; ++b) {
         const int f = 16 * b + 4 * gq;
-        X[16 + b] = make_float4(rad_small_feature(f, xs, vs, ns, a.nfreq_view, view),
+        X[KF + b] = make_float4(rad_small_feature(f, xs, vs, ns, a.nfreq_view, view),
                                 rad_small_feature(f + 1, xs, vs, ns, a.nfreq_view, view),
                                 rad_small_feature(f + 2, xs, vs, ns, a.nfreq_view, view),
                                 rad_small_feature(f + 3, xs, vs, ns, a.nfreq_view, view));
       }
+      if constexpr (FOLD) {
 #pragma unroll
-      for (int b = 0; b < 16; ++b) X[b] = *(const float4*)(a.feature + pc * 256 + 16 * b + 4 * g);
+        for (int b = 0; b < 16; ++b) ufold[q][b] = *(const float4*)(a.feature + pc * 256 + 16 * b + 4 * g);
+        float mu = 0.0f;
+#pragma unroll
+        for (int b = 0; b < 16; b += 2) mu = amax8(mu, ufold[q][b], ufold[q][b + 1]);
+        umax[q] = max4_groups(mu);
+      } else {
+#pragma unroll
+        for (int b = 0; b < 16; ++b) X[b] = *(const float4*)(a.feature + pc * 256 + 16 * b + 4 * g);
+        umax[q] = 0.0f;
+      }
       float m = 0.0f;
 #pragma unroll
-      for (int b = 0; b < 16 + KBS; b += 2) m = amax8(m, X[b], X[b + 1]);
+      for (int b = 0; b < K0; b += 2) m = amax8(m, X[b], X[b + 1]);
       m_in[q] = max4_groups(m);
       const float s = bound_scale(m_in[q]);  // exact-max scale of op 0's operand
 #pragma unroll
@@ -2286,8 +2335,16 @@ void rad4_kernel(RadKArgs a) {
     };
     {
       float sc[kNC];
-      next_scales(K0, sc);
-      op4<K0, 16, C16, false, false>(ws, OP(0), OP(1), Uh, Ul, xinv, pd, nopre, ReluEpi4{Vh, Vl, sc, mrun}, lane);
+      if constexpr (FOLD) {  // |z + u| <= R m_small + B + max |u| (R0's bias is zero: b0 rides in u)
+        const float4 v = ws.buf()[2 * K0 * 64 + 8];
+#pragma unroll
+        for (int q = 0; q < kNC; ++q) sc[q] = bound_scale(fmaf(v.y, m_in[q], v.z) + umax[q]);
+        op4<K0, 16, C16, false, false>(ws, OP(0), OP(1), Uh, Ul, xinv, pd, nopre,
+                                       FoldEpi4{Vh, Vl, sc, mrun, ufold}, lane);
+      } else {
+        next_scales(K0, sc);
+        op4<K0, 16, C16, false, false>(ws, OP(0), OP(1), Uh, Ul, xinv, pd, nopre, ReluEpi4{Vh, Vl, sc, mrun}, lane);
+      }
       finish(sc);
     }
     {
@@ -3655,11 +3712,13 @@ static int grid_for(int64_t P, int ppw = kPointsPerWG) {
 
 int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
                float* feature, int nfreq, void* ws, size_t ws_bytes, hipStream_t stream, const int* P_dev,
-               int P_mult) {
+               int P_mult, const void* f8_alt) {
   if (P <= 0) return NR_OK;
   const int grid = grid_for(P);
+  NR_REQUIRE(!f8_alt || (feature && L.prec == NR_PREC_F16X3 && !L.siren), NR_ERR_ARG,
+             "sdf: an op in F8's place needs the f16x3 softplus net and a feature buffer");
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, feature, (float4*)ws, nfreq, P_dev, P_mult, nullptr, nullptr,
-             nullptr};
+             nullptr, (const char*)f8_alt};
   ProfScope prof(nabla ? (feature ? "sdf_nabla_feat" : "sdf_nabla") : (feature ? "sdf_feat" : "sdf_fwd"), (double)P,
                  stream, P_dev, P_mult);
   if (L.siren) {
@@ -3793,10 +3852,13 @@ int launch_radiance_train32(const RadLayout& L, const void* packed, const float*
 
 int launch_radiance(const RadLayout& L, const void* packed, const float* x, const float* vdir, int64_t vdiv,
                     int64_t vmod, const float* normals, const float* feature, int64_t P, float* rgb, int nfreq_view,
-                    hipStream_t stream, const int* P_dev) {
+                    hipStream_t stream, const int* P_dev, const void* r0_fold) {
   if (P <= 0) return NR_OK;
   const int grid = grid_for(P);
-  RadKArgs a{(const char*)packed, L, x, vdir, vdiv, vmod, normals, feature, P, rgb, nfreq_view, P_dev};
+  NR_REQUIRE(!r0_fold || (L.prec == NR_PREC_F16X3 && !L.siren && L.D == 4), NR_ERR_ARG,
+             "radiance: the folded layer 0 needs the f16x3 ReLU D=4 net");
+  RadKArgs a{(const char*)packed, L, x, vdir, vdiv, vmod, normals, feature, P, rgb, nfreq_view, P_dev,
+             (const char*)r0_fold};
   ProfScope prof("radiance", (double)P, stream, P_dev, 1);
   const bool h3 = L.prec == NR_PREC_F16X3;
   // (small-input blocks, activation, depth) variants
@@ -3812,8 +3874,11 @@ int launch_radiance(const RadLayout& L, const void* packed, const float* x, cons
     return NR_ERR_UNSUPPORTED;
   }
   if (h3 && !L.siren && L.D == 4) {  // the v3 pipeline (rad4_kernel)
-    if (L.kbs == 2) hipLaunchKernelGGL((rad4_kernel<2>), dim3(grid), dim3(kT4), 0, stream, a);
-    else hipLaunchKernelGGL((rad4_kernel<4>), dim3(grid), dim3(kT4), 0, stream, a);
+    if (r0_fold) {
+      if (L.kbs == 2) hipLaunchKernelGGL((rad4_kernel<2, true>), dim3(grid), dim3(kT4), 0, stream, a);
+      else hipLaunchKernelGGL((rad4_kernel<4, true>), dim3(grid), dim3(kT4), 0, stream, a);
+    } else if (L.kbs == 2) hipLaunchKernelGGL((rad4_kernel<2, false>), dim3(grid), dim3(kT4), 0, stream, a);
+    else hipLaunchKernelGGL((rad4_kernel<4, false>), dim3(grid), dim3(kT4), 0, stream, a);
   } else if (!L.siren && L.D == 4) {
     if (L.kbs == 2) NR_RAD_LAUNCH(2, ACT_RELU, 4); else NR_RAD_LAUNCH(4, ACT_RELU, 4);
   } else if (!L.siren && L.D == 5) {

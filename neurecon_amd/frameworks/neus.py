@@ -92,7 +92,8 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
                   near_bypass=None, far_bypass=None, detailed_output=True, show_progress=False, perturb=False,
                   fixed_s_recp=1 / 64., N_samples=64, N_importance=64, N_outside=0,
                   upsample_algo='official_solution', N_nograd_samples=2048, N_upsample_iters=4,
-                  skip_zero_alpha=True, defer_sample_nablas=True, max_workspace_gb=None, **dummy_kwargs):
+                  skip_zero_alpha=True, defer_sample_nablas=True, max_workspace_gb=None, fold_feature=True,
+                  **dummy_kwargs):
     """neus.py:118-397, render mode.  skip_zero_alpha (not a reference argument): mid-points whose alpha
     is exactly 0 (and, with NeRF++, the ones outside the bounding sphere) skip the SDF + radiance nets
     when the radiance output is not asked for -- their weight is an exact 0 (or their colour is the
@@ -104,7 +105,12 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
     weight -- bit-identical maps.  Memory: the library renders chunks of at most `rayschunk` rays (the
     reference's memory bound, neus.py:384-397) whose workspace fits max_workspace_gb (not a reference
     argument; None: _lib.set_workspace_budget / $NR_MAX_WORKSPACE_GB / 4 GiB) -- the maps do not depend
-    on the chunking.  rays_o/rays_d: [(B,) N_rays, 3]; rays_d need not be normalized.
+    on the chunking.  fold_feature (not a reference argument; f16x3 softplus SDF net and ReLU D=4 radiance
+    net, else without effect): the geometry-feature layer, which has no activation, is folded into the
+    radiance net's layer 0 once per weight version (RadianceNet.nr_fold_packed), so the mid-points skip one
+    256x256 layer product; sampling, sdf, nablas and weights are bit-identical, radiance differs by layer
+    0's rounding.  False: the feature goes through layer 0 as in the reference.
+    rays_o/rays_d: [(B,) N_rays, 3]; rays_d need not be normalized.
     perturb=True draws the reference's uniforms (same generators, shapes and order) and hands them
     to the kernels."""
     L.require_gpu(rays_o, 'rays_o')
@@ -160,6 +166,8 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
     a.rays_o, a.rays_d, a.n_rays = L.ptr(ro), L.ptr(rd), n
     a.sdf, a.sdf_packed = ctypes.pointer(sdf_desc), L.ptr(sdf_packed)
     a.rad, a.rad_packed = ctypes.pointer(rad_desc), L.ptr(rad_packed)
+    fold_packed = model.radiance_net.nr_fold_packed(model.implicit_surface, dev) if fold_feature else None
+    a.fold_packed = L.ptr(fold_packed)
     a.s, a.s_dev = 0.0, L.ptr(s_dev)
     a.no_mid_skip = 0 if skip_zero_alpha else 1
     a.no_defer = 0 if defer_sample_nablas else 1
