@@ -470,6 +470,39 @@ int nr_sdf_grid(const NrSdfDesc* d, const void* packed, double volume_size, int6
                 float* sdf, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Marching cubes on the device (nr_mcubes.hip): replaces `skimage.measure.marching_cubes`
+ * (utils/mesh_util.py:33-35) inside `convert_sigma_samples_to_ply` (utils/mesh_util.py:13-79).
+ * volume: device fp32 [n0, n1, n2] in C order, every dim >= 2.  A corner is inside iff v < level
+ * (NaN and v == level are outside); one vertex per grid edge with exactly one end inside, one
+ * triangle list per cell from a generated 256-case table.  Vertices are ordered by the owning point's
+ * flat C index, then axis 0, 1, 2; faces by the cell's flat index, then table order: nothing depends
+ * on atomics, two runs are bit-identical.  Normals (right-hand rule) point toward larger values.
+ * Corner / cube-edge numbering and the full definitions: the header comment of nr_mcubes.hip.
+ *   nr_mc_table            host only, no GPU: tri [256 * 16] int8 cube-edge ids, three per triangle,
+ *                          terminated by -1; counts [256] triangles per case (0..5).  utils/mesh_util.py:33-35
+ *   nr_mc_workspace_bytes  5 bytes per grid point + 8 bytes per 256 points + < 1 KiB (0 on bad dims);
+ *                          utils/mesh_util.py:13-79
+ *   nr_mc_count            classify + scan; totals (device int64 [2]) receives {V, F}.  The workspace then
+ *                          carries the state nr_mc_emit needs.  utils/mesh_util.py:33-35
+ *   nr_mc_emit             same volume / dims / level / workspace as the nr_mc_count before it;
+ *                          n_verts / n_faces the totals the caller read (each must fit int32, NR_ERR_ARG
+ *                          otherwise, and the capacities verts_cap / faces_cap, in rows, must cover them:
+ *                          NR_ERR_ARG before any launch); writes verts fp32 [n_verts, 3] and faces int32
+ *                          [n_faces, 3].  Vertex on the edge from point index i along axis a, end values
+ *                          v0, v1: t = (level - v0) / (v1 - v0), index-space coordinate i + t on axis a,
+ *                          pos = ((idx * spacing + origin) / scale) - offset per axis, all in float64,
+ *                          rounded to fp32 once (spacing of utils/mesh_util.py:33-35, transform of :13-79).
+ * ------------------------------------------------------------------------------------------ */
+int nr_mc_table(int8_t* tri, int32_t* counts);
+size_t nr_mc_workspace_bytes(int64_t n0, int64_t n1, int64_t n2);
+int nr_mc_count(const float* volume, int64_t n0, int64_t n1, int64_t n2, float level, void* workspace,
+                size_t workspace_bytes, int64_t* totals, void* stream);
+int nr_mc_emit(const float* volume, int64_t n0, int64_t n1, int64_t n2, float level, const double* spacing,
+               const double* origin, double scale, const double* offset, void* workspace, size_t workspace_bytes,
+               int64_t n_verts, int64_t n_faces, float* verts, int64_t verts_cap, int32_t* faces, int64_t faces_cap,
+               void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training path (models/frameworks/neus.py:417-485, models/base.py:265-282 with
  * create_graph=True).  The host runs the step layer by layer: the dense [P, K] x [K, N] layer
  * products go to hipBLASLt, every per-point / per-ray step between them is one of these kernels.

@@ -204,6 +204,12 @@ _SIGS = {
     'nr_sdf_grid_workspace_bytes': (_c_sz, [_c_i64]),
     'nr_sdf_grid': (_c_i, [ctypes.POINTER(NrSdfDesc), _c_p, ctypes.c_double, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
                            _c_sz, _c_p]),
+    # device marching cubes (nr_mcubes.hip)
+    'nr_mc_table': (_c_i, [_c_p, _c_p]),
+    'nr_mc_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    'nr_mc_count': (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_f, _c_p, _c_sz, _c_p, _c_p]),
+    'nr_mc_emit': (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_f, ctypes.POINTER(_c_d), ctypes.POINTER(_c_d), _c_d,
+                          ctypes.POINTER(_c_d), _c_p, _c_sz, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p]),
     # training path (nr_train.hip)
     'nr_embed': (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_jvp': (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),

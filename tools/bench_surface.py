@@ -1,7 +1,8 @@
 """Throughput of the §8f widening rows on one GPU (not the headline bench):
   * surface_render (sphere tracing, 20 iterations) of a full 800x600 frame (480,000 rays, config-(d) camera);
   * surface_render (root finding: 256-step march + secant) of the same frame, chunked and full march;
-  * extract_mesh's SDF grid query at N=512 (134 M forward SDF evaluations).
+  * extract_mesh's SDF grid query at N=512 (134 M forward SDF evaluations);
+  * marching cubes (nr_mc_count + nr_mc_emit) of that grid at level 0.
 Prints one JSON line per workload with per-kernel HIP-event timings from the library.
 
     python tools/bench_surface.py [--reps 3]
@@ -22,7 +23,7 @@ import torch  # noqa: E402
 import weightgen as wg  # noqa: E402
 from helpers import neus_model  # noqa: E402
 from neurecon_amd import _lib as L, rend_util  # noqa: E402
-from neurecon_amd.mesh_util import sdf_grid  # noqa: E402
+from neurecon_amd.mesh_util import marching_cubes, sdf_grid  # noqa: E402
 from neurecon_amd.ray_casting import surface_render  # noqa: E402
 
 FWD_FLOP = 2 * 524544      # SDF forward, per point
@@ -43,6 +44,21 @@ def timed(fn, reps):
     prof = L.profile_read()
     L.profile_enable(False)
     return out, dt, {k: (v[0] / reps, v[1] / reps) for k, v in prof.items()}
+
+
+def timed_each(fn, reps):
+    """like timed, but the library's event times of every repetition on its own: [{kernel: ms}]"""
+    fn()
+    torch.cuda.synchronize()
+    L.profile_enable(True)
+    L.profile_read()
+    per_rep = []
+    for _ in range(reps):
+        out = fn()
+        torch.cuda.synchronize()
+        per_rep.append({k: v[1] for k, v in L.profile_read().items()})
+    L.profile_enable(False)
+    return out, per_rep
 
 
 def main():
@@ -82,6 +98,18 @@ def main():
                               ms=round(dt * 1e3, 3), points_per_s=round(N ** 3 / dt, 1),
                               sdf_kernel_tflops=round(N ** 3 * FWD_FLOP / (kms * 1e-3) / 1e12, 2) if kms else None,
                               kernels={k: dict(launches=v[0], ms=round(v[1], 3)) for k, v in prof.items()})))
+        # marching cubes of that volume: the four mc_* kernels' event times, per repetition
+        (verts, faces), per_rep = timed_each(lambda: marching_cubes(out, 0.0, spacing=[2.0 / N] * 3, origin=[-1.0] * 3),
+                                             max(args.reps, 5))
+        tot = sorted(sum(v for k, v in r.items() if k.startswith('mc_')) for r in per_rep)
+        med = tot[len(tot) // 2]
+        print(json.dumps(dict(workload=f'marching_cubes N={N} (nr_mc_count + nr_mc_emit)', verts=verts.shape[0],
+                              faces=faces.shape[0], ms_median=round(med, 3), ms_min=round(tot[0], 3),
+                              ms_max=round(tot[-1], 3), reps=len(tot),
+                              workspace_bytes=L.lib().nr_mc_workspace_bytes(N, N, N),
+                              volume_GB_per_s=round(N ** 3 * 4 / (med * 1e-3) / 1e9, 1),
+                              kernels={k: round(sorted(r[k] for r in per_rep)[len(per_rep) // 2], 3)
+                                       for k in per_rep[0] if k.startswith('mc_')})))
 
 
 if __name__ == '__main__':
