@@ -588,7 +588,7 @@ __device__ __forceinline__ float vs_sdf_bg(const float* sdf, const float* pts, i
   masked = false;
   if (use_bg) {
     const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-    const float dbg = fsub(r_bg, __fsqrt_rn(fadd(fadd(fmul(x, x), fmul(y, y)), fmul(z, z))));
+    const float dbg = fsub(r_bg, norm3_ref(x, y, z));  // |x| as the render kernel (nr_volsdf.hip surface_sdf) and torch form it
     if (dbg < v) {
       v = dbg;
       masked = true;
@@ -750,7 +750,7 @@ __global__ void volsdf_composite_bwd_kernel(const float* __restrict__ sdf, const
     }
     if (i < S) {
       const int64_t q = r * S + i;
-      if (g_sdf) vbar += (double)g_sdf[q];
+      vbar += g_sdf ? (double)g_sdf[q] : 0.0;  // NULL as a zero tensor, to the sign of a zero d_sdf
       bool m;
       (void)vs_sdf_bg(sdf, pts, q, use_bg, r_bg, m);
       d_sdf[q] = m ? 0.0f : (float)vbar;

@@ -485,6 +485,7 @@ class NeuSCompositeBG(torch.autograd.Function):
         dev = sdf.device
         sdf, rad, s = sdf.contiguous(), rad.contiguous(), s.reshape(-1)[:1].contiguous()
         sig_o, rad_o = sig_o.contiguous(), rad_o.contiguous()
+        d_out, inside = d_out.contiguous(), inside.contiguous()
         rgb = torch.empty(R, 3, device=dev)
         depth = torch.empty(R, device=dev)
         acc = torch.empty(R, device=dev)
