@@ -503,6 +503,44 @@ int nr_mc_emit(const float* volume, int64_t n0, int64_t n1, int64_t n2, float le
                void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh finishing on the device (nr_meshops.hip): connected components and order-preserving
+ * filtering of an indexed triangle mesh, the "keep the largest component" / "drop components under
+ * k faces" step users of utils/mesh_util.py:82-112 run on its PLY in a separate tool.
+ * faces: device int32 [F, 3] over vertices 0 .. V-1; 0 <= V, F <= INT32_MAX.  Two vertices are in one
+ * component iff a chain of faces connects them; a vertex no face names is a component with 0 faces.
+ * A face index outside [0, V) is never dereferenced: the face is skipped and status bit 0 is set.
+ * Integer atomics only: every result is fully defined, two runs are bit-identical.  The labelling
+ * (lock-free union-find, higher root hooked under the lower by a device-scope CAS), why it cannot
+ * hang and the full definitions: the header comment of nr_meshops.hip.
+ *   nr_mesh_workspace_bytes  256 + 4 bytes per vertex + 4 bytes per 256 vertices and per 256 faces,
+ *                            each array rounded up to 256 bytes (0 on bad counts); one size serves all
+ *                            three calls.
+ *   nr_mesh_components       labels [V]: the smallest vertex index of the vertex's component;
+ *                            face_count [V]: the component's faces, stored at its label, 0 elsewhere;
+ *                            totals (device int64 [4]): {components, label of the largest (most faces,
+ *                            a tie to the smaller label; -1 when V == 0), its face count, status}.
+ *                            status bit 0: a face index outside [0, V); bit 1: an iteration cap was
+ *                            reached (labels unusable; cannot happen, nr_meshops.hip).
+ *   nr_mesh_filter_count     vkeep [V] bytes: a vertex is kept iff vkeep[v] != 0, a face iff its three
+ *                            indices are valid and kept.  totals (device int64 [2]) receives {V', F'}.
+ *                            The workspace then carries the state nr_mesh_filter_emit needs.
+ *   nr_mesh_filter_emit      same faces / counts / vkeep / workspace as the nr_mesh_filter_count before
+ *                            it; Vk / Fk the totals the caller read (Vk <= V, Fk <= F, and the
+ *                            capacities vsrc_cap / faces_cap, in rows, must cover them: NR_ERR_ARG
+ *                            before any launch).  Kept vertices and faces keep their relative order:
+ *                            vsrc int32 [Vk] maps new -> old vertex index (ascending), faces_out int32
+ *                            [Fk, 3] holds the kept faces with new indices.
+ * ------------------------------------------------------------------------------------------ */
+size_t nr_mesh_workspace_bytes(int64_t V, int64_t F);
+int nr_mesh_components(const int32_t* faces, int64_t F, int64_t V, int32_t* labels, int32_t* face_count,
+                       int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+int nr_mesh_filter_count(const int32_t* faces, int64_t F, int64_t V, const uint8_t* vkeep, void* workspace,
+                         size_t workspace_bytes, int64_t* totals, void* stream);
+int nr_mesh_filter_emit(const int32_t* faces, int64_t F, int64_t V, const uint8_t* vkeep, void* workspace,
+                        size_t workspace_bytes, int64_t Vk, int64_t Fk, int32_t* vsrc, int64_t vsrc_cap,
+                        int32_t* faces_out, int64_t faces_cap, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training path (models/frameworks/neus.py:417-485, models/base.py:265-282 with
  * create_graph=True).  The host runs the step layer by layer: the dense [P, K] x [K, N] layer
  * products go to hipBLASLt, every per-point / per-ray step between them is one of these kernels.

@@ -210,6 +210,12 @@ _SIGS = {
     'nr_mc_count': (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_f, _c_p, _c_sz, _c_p, _c_p]),
     'nr_mc_emit': (_c_i, [_c_p, _c_i64, _c_i64, _c_i64, _c_f, ctypes.POINTER(_c_d), ctypes.POINTER(_c_d), _c_d,
                           ctypes.POINTER(_c_d), _c_p, _c_sz, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p]),
+    # mesh finishing: components and filtering (nr_meshops.hip)
+    'nr_mesh_workspace_bytes': (_c_sz, [_c_i64, _c_i64]),
+    'nr_mesh_components': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    'nr_mesh_filter_count': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p, _c_p]),
+    'nr_mesh_filter_emit': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_p, _c_i64, _c_p,
+                                   _c_i64, _c_p]),
     # training path (nr_train.hip)
     'nr_embed': (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_jvp': (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),

@@ -23,6 +23,14 @@ are ordered by the owning grid point's flat index, then axis; faces by cell, the
 Note: the reference computes the voxel y / x indices with true division (`(i / N) % N`,
 `((i / N) / N) % N`, mesh_util.py:92-93), i.e. with fractional parts z/N and y/N + z/N^2 of a
 voxel; the grid reproduces that bit for bit (tests/test_gpu_surface.py), it does not "fix" it.
+
+Mesh finishing, all on the device and off by default: `mesh_components` / `filter_mesh` label connected
+components and drop the small ones, keeping the order of what stays (libnrhip `nr_mesh_components`,
+`nr_mesh_filter_count` + `nr_mesh_filter_emit`, neurecon_amd/csrc/nr_meshops.hip); `grid_sample_positions`
+maps a marching-cubes vertex back to the point of space the sheared grid above sampled;
+`vertex_attributes` evaluates normals (the SDF gradient) and colours (the radiance net, seen head-on) there
+with the render path's net kernels; `write_ply` carries both.  `extract_mesh`'s keywords keep / min_faces /
+vertex_normals / vertex_colors / coords chain them.
 """
 import ctypes
 
@@ -117,28 +125,240 @@ def marching_cubes(volume, level=0.0, spacing=(1., 1., 1.), origin=(0., 0., 0.),
     return verts, faces
 
 
+def _mesh_faces(faces, n_verts):
+    L.require_gpu(faces, 'faces')
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'faces must be an integer tensor [F, 3], got {faces.dtype} {tuple(faces.shape)}')
+    V = int(n_verts)
+    if not 0 <= V < 2 ** 31 or faces.shape[0] >= 2 ** 31:
+        raise ValueError(f'{V} vertices / {faces.shape[0]} faces do not fit int32 indices')
+    if faces.dtype == torch.int64:  # an index beyond int32 must stay out of range after the cast
+        faces = faces.clamp(-1, 2 ** 31 - 1)
+    return faces.detach().to(torch.int32).contiguous(), V
+
+
+def _components(faces, V):
+    """-> labels [V], face_count [V] (int32, device), totals: host ints (components, largest label, its faces)"""
+    dev = faces.device
+    F = faces.shape[0]
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = lib.nr_mesh_workspace_bytes(V, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        labels = torch.empty(V, dtype=torch.int32, device=dev)
+        face_count = torch.empty(V, dtype=torch.int32, device=dev)
+        totals = torch.empty(4, dtype=torch.int64, device=dev)
+        L.check(lib.nr_mesh_components(L.ptr(faces), F, V, L.ptr(labels), L.ptr(face_count), L.ptr(totals), L.ptr(ws),
+                                       ws_bytes, L.stream_of(dev)))
+        n, largest, largest_faces, status = (int(x) for x in totals.cpu())  # the one host read: 32 bytes
+    if status & 1:
+        raise ValueError(f'faces name a vertex outside [0, {V})')
+    if status:
+        raise L.NrError(f'nr_mesh_components: status {status} (an iteration cap was reached)')
+    return labels, face_count, (n, largest, largest_faces)
+
+
+def mesh_components(faces, n_verts, return_largest=False):
+    """Connected components of an indexed triangle mesh on the device (libnrhip `nr_mesh_components`):
+    faces [F, 3] integer device tensor over vertices 0 .. n_verts-1 -> (labels [V] int32: the smallest vertex
+    index of the vertex's component; face_count [V] int32: the component's faces, stored at its label, 0
+    elsewhere; n_components: int).  A vertex no face names is a component with 0 faces.  With
+    `return_largest` also (label, faces) of the component with most faces (a tie: the smaller label).
+    Fully defined, so two runs are bit-identical; definitions: neurecon_amd/csrc/nr_meshops.hip.
+    Raises ValueError when a face names a vertex outside [0, n_verts)."""
+    faces, V = _mesh_faces(faces, n_verts)
+    labels, face_count, (n, largest, largest_faces) = _components(faces, V)
+    if return_largest:
+        return labels, face_count, n, (largest, largest_faces)
+    return labels, face_count, n
+
+
+def filter_mesh(verts, faces, keep='all', min_faces=0, vertex_mask=None):
+    """Drop parts of an indexed mesh on the device, keeping the order of what stays -> (verts', faces', index).
+    keep='largest': only the connected component with most faces (a tie: the one with the smaller label);
+    min_faces=k: only components with at least k faces; vertex_mask [V] bool: only these vertices (the three
+    combine with `and`).  A face stays iff its three vertices stay.  `index` [V'] int64 maps new -> old vertex,
+    ascending: verts' = verts[index], and any other per-vertex attribute follows with index_select.  With
+    keep='all', min_faces=0 and no mask the inputs are returned untouched (index = arange).  Raises ValueError
+    when nothing stays."""
+    if keep not in ('all', 'largest'):
+        raise ValueError(f"keep must be 'all' or 'largest', got {keep!r}")
+    min_faces = int(min_faces)
+    if min_faces < 0:
+        raise ValueError(f'min_faces must be >= 0, got {min_faces}')
+    L.require_gpu(verts, 'verts')
+    if verts.dim() != 2:
+        raise ValueError(f'verts must be [V, C], got {tuple(verts.shape)}')
+    dev = verts.device
+    if keep == 'all' and min_faces == 0 and vertex_mask is None:
+        return verts, faces, torch.arange(verts.shape[0], device=dev)
+    f32, V = _mesh_faces(faces, verts.shape[0])
+    F = f32.shape[0]
+    mask = None
+    if keep == 'largest' or min_faces > 0:
+        labels, face_count, (_, largest, _) = _components(f32, V)
+        if keep == 'largest':
+            mask = labels == largest
+        if min_faces > 0:
+            big = face_count.index_select(0, labels.long()) >= min_faces
+            mask = big if mask is None else mask & big
+    if vertex_mask is not None:
+        vm = torch.as_tensor(vertex_mask, device=dev).reshape(-1) != 0
+        if vm.shape[0] != V:
+            raise ValueError(f'vertex_mask must have one entry per vertex ({V}), got {vm.shape[0]}')
+        mask = vm if mask is None else mask & vm
+    mask = mask.contiguous()
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        ws_bytes = lib.nr_mesh_workspace_bytes(V, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        st = L.stream_of(dev)
+        L.check(lib.nr_mesh_filter_count(L.ptr(f32), F, V, L.ptr(mask), L.ptr(ws), ws_bytes, L.ptr(totals), st))
+        Vk, Fk = (int(x) for x in totals.cpu())  # the one host read: 16 bytes
+        if Vk == 0:
+            raise ValueError('filter_mesh: no vertex is left')
+        vsrc = torch.empty(Vk, dtype=torch.int32, device=dev)
+        faces_out = torch.empty((Fk, 3), dtype=torch.int32, device=dev)
+        L.check(lib.nr_mesh_filter_emit(L.ptr(f32), F, V, L.ptr(mask), L.ptr(ws), ws_bytes, Vk, Fk, L.ptr(vsrc), Vk,
+                                        L.ptr(faces_out), Fk, st))
+    index = vsrc.long()
+    return verts.index_select(0, index), faces_out.to(faces.dtype), index
+
+
+def grid_sample_positions(idx, volume_size, N):
+    """Index-space coordinates (a, b, c) of extract_mesh's N^3 grid [..., 3] -> the point of space the grid
+    sampled there, fp32 [..., 3]: ((a + b/N + c/N^2) step - s/2, (b + c/N) step - s/2, c step - s/2) with
+    step = s / (N - 1), i.e. the reference's sheared lattice (mesh_util.py:92-100), not the s / N lattice its
+    writer assumes (:112).  At integer indices the float64 value is the reference's own, operation for
+    operation (flat index i = (a N + b) N + c; i % N, (i / N) % N, ((i / N) / N) % N; * step + origin); between
+    them the map is affine, so it is evaluated as the multilinear blend of the eight surrounding lattice
+    points in float64 (weights 0 and 1 at integer indices: exact) and rounded to fp32 once.  A marching-cubes
+    vertex at parameter t on a grid edge thus lands at parameter t between the two sampled points.  Index-space
+    vertices come from `marching_cubes(vol, level)` with unit spacing and zero origin.  Plain torch."""
+    N = int(N)
+    if N < 2:
+        raise ValueError(f'grid_sample_positions needs N >= 2, got {N}')
+    idx = torch.as_tensor(idx)
+    if idx.shape[-1] != 3:
+        raise ValueError(f'idx must be [..., 3], got {tuple(idx.shape)}')
+    s = volume_size
+    step, origin = s / (N - 1), -s / 2.
+    p = idx.to(torch.float64)
+    lo = p.floor().clamp(0, N - 2)
+    t = p - lo
+
+    n = torch.full_like(p[..., 0], N)  # a tensor: a device division by a scalar multiplies by its reciprocal
+
+    def lattice(a, b, c):  # mesh_util.py:87-100 at integer a, b, c
+        i = (a * N + b) * N + c
+        x2 = torch.fmod(i, n)
+        x1 = torch.fmod(i / n, n)
+        x0 = torch.fmod((i / n) / n, n)
+        return torch.stack([x0 * step + origin, x1 * step + origin, x2 * step + origin], -1)
+
+    out = torch.zeros_like(p)
+    for corner in range(8):
+        d = [(corner >> 2) & 1, (corner >> 1) & 1, corner & 1]
+        w = torch.ones_like(p[..., 0])
+        for q in range(3):
+            w = w * (t[..., q] if d[q] else 1.0 - t[..., q])
+        out = out + w[..., None] * lattice(lo[..., 0] + d[0], lo[..., 1] + d[1], lo[..., 2] + d[2])
+    return out.to(torch.float32)
+
+
+_ATTR_CHUNK = 1 << 20  # points per net launch of vertex_attributes
+
+
+def vertex_attributes(model, positions, normals=True, colors=False, chunk=None):
+    """Per-vertex normals and colours of a surface at `positions` [V, 3] (device) -> (normals or None, colors or
+    None), fp32 [V, 3].  `model`: a NeuS / VolSDF / UNISURF model, or an ImplicitSurface (normals only).
+    Normals: F.normalize(nablas, dim=-1) of implicit_surface.forward_with_nablas: the SDF gradient, toward
+    larger values like the face orientation.  Colours: model.forward(positions, view_dirs=-normals)[0]: the
+    surface seen head-on.  Runs on the render path's net kernels under no_grad, in chunks; nothing else is
+    computed here."""
+    L.require_gpu(positions, 'positions')
+    if positions.dim() != 2 or positions.shape[1] != 3:
+        raise ValueError(f'positions must be [V, 3], got {tuple(positions.shape)}')
+    surface = getattr(model, 'implicit_surface', model)
+    if colors and surface is model:
+        raise ValueError('vertex_attributes: colors need a model with a radiance net, not an ImplicitSurface')
+    if not (normals or colors):
+        return None, None
+    chunk = int(chunk or _ATTR_CHUNK)
+    pos = positions.detach().float().contiguous()
+    ns, cs = [], []
+    with torch.no_grad():
+        for j in range(0, pos.shape[0], chunk):
+            x = pos[j:j + chunk]
+            n = torch.nn.functional.normalize(surface.forward_with_nablas(x)[1], dim=-1)
+            ns.append(n)
+            if colors:
+                cs.append(model.forward(x, view_dirs=-n)[0])
+    empty = pos.new_zeros((0, 3))
+    n_all = torch.cat(ns) if ns else empty
+    c_all = (torch.cat(cs) if cs else empty) if colors else None
+    return (n_all if normals else None), c_all
+
+
 def _host(a, dtype):
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
     return np.asarray(a).astype(dtype, copy=False)
 
 
-def write_ply(path, verts, faces):
+def _host_colors(colors):
+    """uint8 as given; float: floor(clamp(c, 0, 1) * 255 + 0.5), evaluated in float64 (NaN -> 0)"""
+    if isinstance(colors, torch.Tensor):
+        colors = colors.detach().cpu().numpy()
+    c = np.asarray(colors)
+    if c.dtype == np.uint8:
+        return c
+    if not np.issubdtype(c.dtype, np.floating):
+        raise ValueError(f'write_ply: colors must be uint8 or float, got {c.dtype}')
+    c = np.nan_to_num(c.astype(np.float64), nan=0.0)
+    return np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY of an indexed triangle mesh, the elements plyfile writes for the reference
     (mesh_util.py:59-74): vertex x/y/z as float, face vertex_indices as `list uchar int`.  verts [V, 3],
-    faces [F, 3]: numpy arrays or tensors (device tensors are copied to the host)."""
+    faces [F, 3]: numpy arrays or tensors (device tensors are copied to the host).  normals [V, 3] add
+    `property float nx/ny/nz` after x y z, colors [V, 3] then `property uchar red/green/blue` (uint8 as given,
+    float quantised as floor(clamp(c, 0, 1) * 255 + 0.5)); with neither, the layout above, byte for byte."""
     v, f = _host(verts, '<f4'), _host(faces, '<i4')
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError(f'write_ply needs verts [V, 3] and faces [F, 3], got {v.shape} and {f.shape}')
-    header = (f'ply\nformat binary_little_endian 1.0\nelement vertex {v.shape[0]}\n'
-              'property float x\nproperty float y\nproperty float z\n'
+    fields, props = [('xyz', '<f4', (3,))], 'property float x\nproperty float y\nproperty float z\n'
+    n = c = None
+    if normals is not None:
+        n = _host(normals, '<f4')
+        fields.append(('n', '<f4', (3,)))
+        props += 'property float nx\nproperty float ny\nproperty float nz\n'
+    if colors is not None:
+        c = _host_colors(colors)
+        fields.append(('rgb', 'u1', (3,)))
+        props += 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+    for name, a in (('normals', n), ('colors', c)):
+        if a is not None and a.shape != v.shape:
+            raise ValueError(f'write_ply needs {name} {v.shape} like verts, got {a.shape}')
+    header = (f'ply\nformat binary_little_endian 1.0\nelement vertex {v.shape[0]}\n' + props +
               f'element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n')
     rec = np.empty(f.shape[0], dtype=np.dtype([('n', 'u1'), ('vertex_indices', '<i4', (3,))]))  # packed: 13 bytes
     rec['n'] = 3
     rec['vertex_indices'] = f
     with open(path, 'wb') as out:
         out.write(header.encode('ascii'))
-        np.ascontiguousarray(v).tofile(out)
+        if n is None and c is None:
+            np.ascontiguousarray(v).tofile(out)
+        else:
+            vrec = np.empty(v.shape[0], dtype=np.dtype(fields))  # packed: 12 / 24 / 15 / 27 bytes
+            vrec['xyz'] = v
+            if n is not None:
+                vrec['n'] = n
+            if c is not None:
+                vrec['rgb'] = c
+            vrec.tofile(out)
         rec.tofile(out)
 
 
@@ -198,15 +418,51 @@ def convert_sigma_samples_to_ply(input_3d_sigma_array, voxel_grid_origin, volume
 
 
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath='./surface.ply', show_progress=True,
-                 chunk=16 * 1024, marching='auto'):
+                 chunk=16 * 1024, marching='auto', keep='all', min_faces=0, vertex_normals=False,
+                 vertex_colors=False, model=None, coords='reference'):
     """mesh_util.py:82-112, its quirks included: the grid is sampled with step s / (N - 1) but handed to
     marching cubes with spacing s / N and origin -s / 2 (:84, :112).  Writes `filepath`, returns None.
     `chunk` is accepted for API compatibility (the device grid uses larger launches).  On the native
-    marching path the volume stays on the device."""
+    marching path the volume stays on the device.
+
+    Mesh finishing (native marching only; with all of these at their defaults the call is the one above):
+    keep='largest' / min_faces=k drop connected components (`filter_mesh`); vertex_normals / vertex_colors
+    add per-vertex nx ny nz / red green blue (`vertex_attributes`; colours need `model`, the NeuS / VolSDF /
+    UNISURF model that owns `implicit_surface`); coords='sampled' writes each vertex at the point of space
+    the grid sampled (`grid_sample_positions`: the un-sheared, correctly scaled mesh) instead of the
+    reference's s / N lattice.  Attributes are always evaluated at the sampled positions, whichever
+    coordinates are written.  Order: marching cubes, filter, attributes on the surviving vertices."""
     s = volume_size
-    out = sdf_grid(implicit_surface, s, N)
-    if _marching_mode(marching) != 'native':
-        out = out.cpu().numpy()
-    convert_sigma_samples_to_ply(out, [-s / 2., -s / 2., -s / 2.], [float(s) / N] * 3, filepath, level=level,
-                                 marching=marching)
+    mode = _marching_mode(marching)
+    if coords not in ('reference', 'sampled'):
+        raise ValueError(f"coords must be 'reference' or 'sampled', got {coords!r}")
+    options = dict(keep=keep != 'all', min_faces=min_faces != 0, vertex_normals=bool(vertex_normals),
+                   vertex_colors=bool(vertex_colors), coords=coords != 'reference')
+    used = [k for k, v in options.items() if v]
+    if not used:
+        out = sdf_grid(implicit_surface, s, N)
+        if mode != 'native':
+            out = out.cpu().numpy()
+        convert_sigma_samples_to_ply(out, [-s / 2., -s / 2., -s / 2.], [float(s) / N] * 3, filepath, level=level,
+                                     marching=marching)
+        return
+    if mode != 'native':
+        raise ValueError(f"extract_mesh: {used[0]} needs marching='native' (marching={marching!r} resolved to the "
+                         'scikit-image path, which has no mesh finishing)')
+    if vertex_colors and model is None:
+        raise ValueError('extract_mesh: vertex_colors=True needs model= (the model whose radiance net gives the colours)')
+    vol = sdf_grid(implicit_surface, s, N)
+    idx, faces = marching_cubes(vol, level=level)  # index space: unit spacing, zero origin
+    if coords == 'reference':  # the vertices of the default call, bit for bit
+        verts, _ = marching_cubes(vol, level=level, spacing=[float(s) / N] * 3, origin=[-s / 2., -s / 2., -s / 2.])
+    else:
+        verts = grid_sample_positions(idx, s, N)
+    del vol
+    verts, faces, index = filter_mesh(verts, faces, keep=keep, min_faces=min_faces)
+    normals = colors = None
+    if vertex_normals or vertex_colors:
+        pos = verts if coords == 'sampled' else grid_sample_positions(idx.index_select(0, index), s, N)
+        normals, colors = vertex_attributes(model if vertex_colors else implicit_surface, pos,
+                                            normals=vertex_normals, colors=vertex_colors)
+    write_ply(filepath, verts, faces, normals=normals, colors=colors)
 

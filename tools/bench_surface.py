@@ -2,7 +2,8 @@
   * surface_render (sphere tracing, 20 iterations) of a full 800x600 frame (480,000 rays, config-(d) camera);
   * surface_render (root finding: 256-step march + secant) of the same frame, chunked and full march;
   * extract_mesh's SDF grid query at N=512 (134 M forward SDF evaluations);
-  * marching cubes (nr_mc_count + nr_mc_emit) of that grid at level 0.
+  * marching cubes (nr_mc_count + nr_mc_emit) of that grid at level 0;
+  * mesh finishing of that mesh: components, the keep-largest filter, per-vertex normals and colours.
 Prints one JSON line per workload with per-kernel HIP-event timings from the library.
 
     python tools/bench_surface.py [--reps 3]
@@ -23,7 +24,8 @@ import torch  # noqa: E402
 import weightgen as wg  # noqa: E402
 from helpers import neus_model  # noqa: E402
 from neurecon_amd import _lib as L, rend_util  # noqa: E402
-from neurecon_amd.mesh_util import marching_cubes, sdf_grid  # noqa: E402
+from neurecon_amd.mesh_util import (filter_mesh, grid_sample_positions, marching_cubes, mesh_components,  # noqa: E402
+                                    sdf_grid, vertex_attributes)
 from neurecon_amd.ray_casting import surface_render  # noqa: E402
 
 FWD_FLOP = 2 * 524544      # SDF forward, per point
@@ -110,6 +112,31 @@ def main():
                               volume_GB_per_s=round(N ** 3 * 4 / (med * 1e-3) / 1e9, 1),
                               kernels={k: round(sorted(r[k] for r in per_rep)[len(per_rep) // 2], 3)
                                        for k in per_rep[0] if k.startswith('mc_')})))
+        # mesh finishing on that mesh: components + keep-largest filter (the mesh_* kernels), then normals
+        # and colours at the surviving vertices' sampled positions (the net kernels), per repetition
+        idx, _ = marching_cubes(out, 0.0)
+        del out
+
+        def medians(per_rep, prefix=''):
+            tot = sorted(sum(v for k, v in r.items() if k.startswith(prefix)) for r in per_rep)
+            kernels = {k: round(sorted(r.get(k, 0.0) for r in per_rep)[len(per_rep) // 2], 3)
+                       for k in per_rep[0] if k.startswith(prefix)}
+            return dict(ms_median=round(tot[len(tot) // 2], 3), ms_min=round(tot[0], 3), ms_max=round(tot[-1], 3),
+                        reps=len(tot), kernels=kernels)
+        (_, _, n_comp), per_rep = timed_each(lambda: mesh_components(faces, verts.shape[0]), max(args.reps, 5))
+        print(json.dumps(dict(workload=f'mesh_components N={N} (nr_mesh_components)', verts=verts.shape[0],
+                              faces=faces.shape[0], components=n_comp, **medians(per_rep, 'mesh_'))))
+        (v2, f2, index), per_rep = timed_each(lambda: filter_mesh(verts, faces, keep='largest'), max(args.reps, 5))
+        print(json.dumps(dict(workload=f"filter_mesh keep='largest' N={N} (nr_mesh_components + nr_mesh_filter_count "
+                                       '+ nr_mesh_filter_emit)', verts=verts.shape[0], faces=faces.shape[0],
+                              verts_kept=v2.shape[0], faces_kept=f2.shape[0],
+                              workspace_bytes=L.lib().nr_mesh_workspace_bytes(verts.shape[0], faces.shape[0]),
+                              **medians(per_rep, 'mesh_'))))
+        pos = grid_sample_positions(idx.index_select(0, index), 2.0, N)
+        for colors in (False, True):
+            _, per_rep = timed_each(lambda: vertex_attributes(m, pos, normals=True, colors=colors), max(args.reps, 5))
+            print(json.dumps(dict(workload=f'vertex_attributes N={N} normals' + (' + colours' if colors else ''),
+                                  verts=pos.shape[0], **medians(per_rep))))
 
 
 if __name__ == '__main__':
