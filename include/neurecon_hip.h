@@ -541,6 +541,63 @@ int nr_mesh_filter_emit(const int32_t* faces, int64_t F, int64_t V, const uint8_
                         int32_t* faces_out, int64_t faces_cap, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh rendering on the device (nr_meshrender.hip): depth, normals, barycentrics, face ids and a shaded
+ * frame of an indexed triangle mesh, replacing the Open3D Visualizer pass of tools/render_view.py:438-486
+ * (`--render_mesh`).  Pixel (i, j) = (column, row) is sampled exactly where nr_get_rays shoots its ray
+ * (integer pixel coordinates, the real principal point), so a mesh frame overlays the volume-rendered
+ * frame of the same camera pixel for pixel.  A visibility-buffer rasteriser: vertices are projected in
+ * float64 and snapped to 1/256 pixel, coverage is decided by int64 edge functions with a top-left rule,
+ * the nearest face of a pixel is the 64-bit atomic minimum of (fp32 depth bits << 32 | face index), and
+ * a resolve pass recomputes everything else from the winning face.  Every output is a pure function of
+ * the inputs (two runs are bit-identical; a depth tie goes to the smaller face index).  Faces are
+ * two-sided.  No polygon clipping: a face with a vertex closer than `near` (camera-space z), not finite,
+ * or projected beyond 2^20 pixels is dropped whole and counted.  The rule in full: the header comment of
+ * nr_meshrender.hip.
+ *   verts fp32 [V, 3] world space; faces int32 [F, 3]; normals / colors fp32 [V, 3] or NULL (flat face
+ *   normal / the constant `base`); 0 <= V <= INT32_MAX, 0 <= F < INT32_MAX, H W < 2^31.
+ *   w2c: rows 0..2 of the world -> camera matrix [3][4], m: c2w[:3, :3] [3][3], both row-major doubles;
+ *   fx, fy, cx, cy, skew: intrinsics K[0][0], K[1][1], K[0][2], K[1][2], K[0][1].
+ *   large_threshold: a face whose clipped bounding box holds more pixel samples is rasterised by a whole
+ *   workgroup instead of its own lane (same result either way).
+ *   Outputs (each may be NULL), row-major [H, W(, 3)]: rgb = base (ambient + (1 - ambient) |n . d|)
+ *   (`background` at a miss), depth = distance along the normalised world ray, zdepth = camera-space z,
+ *   normal (world, unit), bary (perspective-correct, of the face's vertices in stored order), mask u8,
+ *   face_id int32 (-1 at a miss); all 0 at a miss but rgb and face_id.
+ *   counters (device int64 [3], may be NULL): faces clipped, degenerate (zero snapped area or an index
+ *   outside [0, V): never dereferenced), queued for the large path.
+ *   nr_mesh_render_workspace_bytes  256 + 32 bytes per vertex + 8 per pixel + 4 per face, each array
+ *                                   rounded up to 256 bytes (0 on bad counts).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* verts;
+  const int32_t* faces;
+  const float* normals;
+  const float* colors;
+  int64_t V, F, H, W;
+  double w2c[12];
+  double m[9];
+  double fx, fy, cx, cy, skew;
+  double near;
+  int64_t large_threshold;
+  double ambient;
+  double base[3];
+  double background[3];
+  float* rgb;       /* [H, W, 3] */
+  float* depth;     /* [H, W]    */
+  float* normal;    /* [H, W, 3] */
+  uint8_t* mask;    /* [H, W]    */
+  int32_t* face_id; /* [H, W]    */
+  float* bary;      /* [H, W, 3] */
+  float* zdepth;    /* [H, W]    */
+  int64_t* counters;
+  void* workspace;
+  size_t workspace_bytes;
+} NrMeshRenderArgs;
+
+size_t nr_mesh_render_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int nr_mesh_render(const NrMeshRenderArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training path (models/frameworks/neus.py:417-485, models/base.py:265-282 with
  * create_graph=True).  The host runs the step layer by layer: the dense [P, K] x [K, N] layer
  * products go to hipBLASLt, every per-point / per-ray step between them is one of these kernels.

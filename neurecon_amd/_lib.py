@@ -146,6 +146,17 @@ class NrAdamTensor(ctypes.Structure):
     _fields_ = [('param', _c_p), ('grad', _c_p), ('exp_avg', _c_p), ('exp_avg_sq', _c_p), ('n', _c_i64)]
 
 
+class NrMeshRenderArgs(ctypes.Structure):
+    _fields_ = [
+        ('verts', _c_p), ('faces', _c_p), ('normals', _c_p), ('colors', _c_p),
+        ('V', _c_i64), ('F', _c_i64), ('H', _c_i64), ('W', _c_i64),
+        ('w2c', _c_d * 12), ('m', _c_d * 9), ('fx', _c_d), ('fy', _c_d), ('cx', _c_d), ('cy', _c_d), ('skew', _c_d),
+        ('near', _c_d), ('large_threshold', _c_i64), ('ambient', _c_d), ('base', _c_d * 3), ('background', _c_d * 3),
+        ('rgb', _c_p), ('depth', _c_p), ('normal', _c_p), ('mask', _c_p), ('face_id', _c_p), ('bary', _c_p),
+        ('zdepth', _c_p), ('counters', _c_p), ('workspace', _c_p), ('workspace_bytes', _c_sz),
+    ]
+
+
 class NrKernelStat(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 32), ('launches', _c_i64), ('ms', ctypes.c_double),
                 ('units', ctypes.c_double)]
@@ -216,6 +227,9 @@ _SIGS = {
     'nr_mesh_filter_count': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p, _c_p]),
     'nr_mesh_filter_emit': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_p, _c_i64, _c_p,
                                    _c_i64, _c_p]),
+    # mesh rendering (nr_meshrender.hip)
+    'nr_mesh_render_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'nr_mesh_render': (_c_i, [ctypes.POINTER(NrMeshRenderArgs), _c_p]),
     # training path (nr_train.hip)
     'nr_embed': (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_jvp': (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),

@@ -31,6 +31,15 @@ maps a marching-cubes vertex back to the point of space the sheared grid above s
 `vertex_attributes` evaluates normals (the SDF gradient) and colours (the radiance net, seen head-on) there
 with the render path's net kernels; `write_ply` carries both.  `extract_mesh`'s keywords keep / min_faces /
 vertex_normals / vertex_colors / coords chain them.
+
+Looking at the result, also on the device: `read_ply` reads the PLY back (the layouts `write_ply` writes, and
+the same elements as ASCII), `render_mesh` turns a mesh into a shaded frame, a depth map comparable with
+`volume_render`'s depth, normals, barycentrics and a face-id map (libnrhip `nr_mesh_render`,
+neurecon_amd/csrc/nr_meshrender.hip), standing in for the Open3D pass of tools/render_view.py:438-486.  It
+samples exactly the pixels `rend_util.get_rays` shoots through, with the real principal point, so a mesh frame
+overlays the volume-rendered frame of the same camera pixel for pixel.  A visibility-buffer rasteriser:
+exact integer coverage on vertices snapped to 1/256 pixel, the nearest face by a 64-bit atomic minimum of
+(depth bits, face index); every output is a pure function of the inputs.
 """
 import ctypes
 
@@ -360,6 +369,226 @@ def write_ply(path, verts, faces, normals=None, colors=None):
                 vrec['rgb'] = c
             vrec.tofile(out)
         rec.tofile(out)
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2',
+              'uint16': 'u2', 'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4',
+              'double': 'f8', 'float64': 'f8'}
+
+
+def _ply_header(data, path):
+    """-> (format, [(element, count, [property tuples])], offset of the body)"""
+    if not data.startswith(b'ply'):
+        raise ValueError(f'read_ply: {path} is not a PLY file')
+    end = data.find(b'end_header')
+    nl = data.find(b'\n', end)
+    if end < 0 or nl < 0:
+        raise ValueError(f'read_ply: {path} has no end_header line')
+    fmt, elements = None, []
+    for line in data[:end].decode('ascii', 'replace').splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ('comment', 'obj_info'):
+            continue
+        if tok[0] == 'format' and len(tok) >= 2:
+            fmt = tok[1]
+        elif tok[0] == 'element' and len(tok) == 3:
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == 'property' and elements and len(tok) in (3, 5):
+            if any(t not in _PLY_TYPES for t in tok[1:-1] if t != 'list') or (len(tok) == 5) != (tok[1] == 'list'):
+                raise ValueError(f'read_ply: {path}: unknown property type in {line!r}')
+            elements[-1][2].append(tuple(tok[1:]))
+        else:
+            raise ValueError(f'read_ply: {path}: cannot parse header line {line!r}')
+    if fmt == 'binary_big_endian':
+        raise ValueError(f'read_ply: {path} is big-endian; only binary_little_endian and ascii are read')
+    if fmt not in ('binary_little_endian', 'ascii'):
+        raise ValueError(f'read_ply: {path}: unknown format {fmt!r}')
+    return fmt, elements, nl + 1
+
+
+def read_ply(path):
+    """Read an indexed triangle mesh from a PLY file -> dict(verts [V, 3] float32, faces [F, 3] int32,
+    normals [V, 3] float32 or None, colors [V, 3] uint8 or None), numpy arrays.  Reads what `write_ply` writes
+    (binary little-endian; 12, 24, 15 or 27 bytes per vertex) and the same elements as ASCII PLY: an element
+    `vertex` with scalar properties, of which x y z, nx ny nz (all three, else None) and red green blue (all
+    three, else None) are kept and every other one is skipped by its declared size, then an element `face`
+    with one list property of vertex indices.  Raises ValueError for a face list that is not all triangles,
+    a big-endian file, a truncated file and anything else it cannot parse."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    fmt, elements, pos = _ply_header(data, path)
+    if [e[0] for e in elements] != ['vertex', 'face']:
+        raise ValueError(f'read_ply: {path}: needs the elements vertex and face, in that order, got '
+                         f'{[e[0] for e in elements]}')
+    (_, V, vprops), (_, F, fprops) = elements
+    if any(p[0] == 'list' for p in vprops) or len(fprops) != 1 or fprops[0][0] != 'list':
+        raise ValueError(f'read_ply: {path}: needs scalar vertex properties and one list property per face')
+    names = [p[1] for p in vprops]
+    if len(set(names)) != len(names) or not all(k in names for k in 'xyz'):
+        raise ValueError(f'read_ply: {path}: vertex properties {names} must be distinct and hold x, y, z')
+    _, count_t, index_t, _ = fprops[0]
+    if fmt == 'ascii':
+        tok = data[pos:].split()
+        nv = V * len(names)
+        if len(tok) < nv + 4 * F:
+            if len(tok) > nv and F > 0 and tok[nv] != b'3':
+                raise ValueError(f'read_ply: {path}: only triangle faces are read')
+            raise ValueError(f'read_ply: {path} is truncated')
+        try:
+            vtab = np.array(tok[:nv], dtype=np.float64).reshape(V, len(names))
+            ftab = np.array(tok[nv:nv + 4 * F], dtype=np.int64).reshape(F, 4)
+        except ValueError as e:
+            raise ValueError(f'read_ply: {path}: bad number in the body') from e
+        if (ftab[:, 0] != 3).any():
+            raise ValueError(f'read_ply: {path}: only triangle faces are read')
+        if len(tok) != nv + 4 * F:
+            raise ValueError(f'read_ply: {path}: {len(tok) - nv - 4 * F} extra values after the faces')
+        col = {n: vtab[:, k].astype(_PLY_TYPES[vprops[k][0]]) for k, n in enumerate(names)}
+        idx = ftab[:, 1:]
+    else:
+        vdt = np.dtype([(n, '<' + _PLY_TYPES[p[0]]) for n, p in zip(names, vprops)])
+        fdt = np.dtype([('n', '<' + _PLY_TYPES[count_t]), ('v', '<' + _PLY_TYPES[index_t], (3,))])
+        body = len(data) - pos - V * vdt.itemsize
+        if body < 0:
+            raise ValueError(f'read_ply: {path} is truncated')
+        if F > 0 and body >= fdt['n'].itemsize and int(np.frombuffer(data, fdt['n'], 1, pos + V * vdt.itemsize)[0]) != 3:
+            raise ValueError(f'read_ply: {path}: only triangle faces are read')
+        if body < F * fdt.itemsize:
+            raise ValueError(f'read_ply: {path} is truncated')
+        vrec = np.frombuffer(data, vdt, V, pos)
+        frec = np.frombuffer(data, fdt, F, pos + V * vdt.itemsize)
+        if (frec['n'] != 3).any():
+            raise ValueError(f'read_ply: {path}: only triangle faces are read')
+        if body != F * fdt.itemsize:
+            raise ValueError(f'read_ply: {path}: {body - F * fdt.itemsize} extra bytes after the faces')
+        col = {n: vrec[n] for n in names}
+        idx = frec['v']
+
+    def cols(keys, dtype):
+        return np.stack([col[k] for k in keys], 1).astype(dtype) if all(k in col for k in keys) else None
+    rgb = ('red', 'green', 'blue')
+    colors = cols(rgb, np.uint8) if all(k in col and col[k].dtype == np.uint8 for k in rgb) else cols(rgb, np.float32)
+    if idx.size and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+        raise ValueError(f'read_ply: {path}: a vertex index does not fit int32')
+    return dict(verts=cols('xyz', np.float32), faces=np.ascontiguousarray(idx).astype(np.int32),
+                normals=cols(('nx', 'ny', 'nz'), np.float32), colors=colors)
+
+
+_LARGE_THRESHOLD = 64  # pixel samples in a face's box above which a workgroup rasterises it
+
+
+def _dev_array(a, dtype, dev, name, V=None):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != 2 or t.shape[1] != 3 or (V is not None and t.shape[0] != V):
+        raise ValueError(f'render_mesh: {name} must be [{"V" if V is None else V}, 3], got {tuple(t.shape)}')
+    return t.detach().to(device=dev, dtype=dtype).contiguous()
+
+
+def render_mesh(verts, faces=None, c2w=None, intrinsics=None, H=None, W=None, normals=None, colors=None, near=1e-4,
+                ambient=0.3, base_color=(0.7, 0.7, 0.7), background=1.0, large_threshold=None):
+    """Render an indexed triangle mesh on the device (libnrhip `nr_mesh_render`, neurecon_amd/csrc/
+    nr_meshrender.hip) through the pixels `rend_util.get_rays(c2w, intrinsics, H, W)` shoots its rays through:
+    integer pixel coordinates and the real principal point, so the frame overlays the volume-rendered frame
+    of the same camera pixel for pixel.  Stands in for the Open3D pass of tools/render_view.py:438-486.
+
+    verts [V, 3], faces [F, 3], normals / colors [V, 3] or None: tensors or arrays -- or `verts` is the dict
+    `read_ply` returns (its normals and colours are used unless given here).  colors: uint8, or float in
+    [0, 1].  c2w [4, 4] or [B, 4, 4] (a loop over the cameras; outputs are stacked), intrinsics [4, 4] / [3, 3]
+    (or one per camera).  The camera is taken in float64 as given; world -> camera is np.linalg.inv of the
+    float64 c2w, on the host.  get_rays works on the fp32 camera: hand both the same fp32 values.
+
+    -> dict of device tensors: rgb [H, W, 3] = base (ambient + (1 - ambient) |n . d|), `background` at a miss;
+    depth [H, W]: distance along the normalised ray (volume_render's depth), 0 at a miss; depth_z [H, W]:
+    camera-space z; normal [H, W, 3]: world space, unit (the blend of the vertex normals, else the face
+    normal); mask [H, W] bool; face_id [H, W] int32, -1 at a miss; bary [H, W, 3]: perspective-correct weights
+    of the face's three vertices; n_clipped: int64 scalar tensor, faces dropped whole because a vertex lies
+    closer than `near`, is not finite or projects beyond 2^20 pixels (there is no polygon clipping);
+    n_degenerate: faces skipped for zero snapped area or an index outside [0, V); n_large: faces that took the
+    workgroup-per-face path (both int64 scalar tensors).
+    Faces are two-sided; the nearest wins, a depth tie goes to the smaller face index; every output is a
+    pure function of the inputs.  large_threshold: box size (pixel samples) above which a face takes the
+    workgroup-per-face path; the result does not depend on it."""
+    if isinstance(verts, dict):
+        mesh = verts
+        verts = mesh['verts']
+        faces = mesh['faces'] if faces is None else faces
+        normals = mesh.get('normals') if normals is None else normals
+        colors = mesh.get('colors') if colors is None else colors
+    if faces is None or c2w is None or intrinsics is None or H is None or W is None:
+        raise ValueError('render_mesh needs verts, faces, c2w, intrinsics, H and W')
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+        raise ValueError(f'render_mesh: needs H, W > 0 and H * W < 2^31, got {H} x {W}')
+    dev = next((t.device for t in (verts, faces, c2w) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError('neurecon_amd: render_mesh needs a GPU (ROCm) device; the path is HIP-only')
+        dev = torch.device('cuda', torch.cuda.current_device())
+    v = _dev_array(verts, torch.float32, dev, 'verts')
+    V = v.shape[0]
+    ft = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(faces))
+    f, _ = _mesh_faces(ft.reshape(-1, 3).to(dev) if ft.numel() == 0 else ft.to(dev), V)  # no face: any shape
+    F = f.shape[0]
+    if F >= 2 ** 31 - 1:
+        raise ValueError(f'render_mesh: {F} faces do not fit the 31-bit face index')
+    n = None if normals is None else _dev_array(normals, torch.float32, dev, 'normals', V)
+    c = None
+    if colors is not None:
+        ct = colors if isinstance(colors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(colors))
+        c = _dev_array(ct, torch.float32, dev, 'colors', V)
+        if ct.dtype == torch.uint8:
+            c = c / torch.full_like(c, 255.0)  # a true division (by a scalar it would multiply by 1 / 255)
+
+    def host64(x):
+        return (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).astype(np.float64)
+    poses, Ks = host64(c2w), host64(intrinsics)
+    batched = poses.ndim == 3
+    if poses.shape[-2:] != (4, 4) or poses.ndim not in (2, 3):
+        raise ValueError(f'render_mesh: c2w must be [4, 4] or [B, 4, 4], got {poses.shape}')
+    poses = poses.reshape(-1, 4, 4)
+    if Ks.ndim not in (2, 3) or Ks.shape[-2:] not in ((4, 4), (3, 3)):
+        raise ValueError(f'render_mesh: intrinsics must be [4, 4] or [3, 3] (or one per camera), got {Ks.shape}')
+    Ks = np.broadcast_to(Ks.reshape(-1, *Ks.shape[-2:]), (poses.shape[0], *Ks.shape[-2:]))
+    lt = _LARGE_THRESHOLD if large_threshold is None else int(large_threshold)
+    if lt < 0:
+        raise ValueError(f'render_mesh: large_threshold must be >= 0, got {lt}')
+    base, bg = _vec3(base_color, 'base_color'), _vec3(background, 'background')
+    lib = L.lib()
+    frames = []
+    with torch.cuda.device(dev):
+        ws_bytes = lib.nr_mesh_render_workspace_bytes(V, F, H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        st = L.stream_of(dev)
+        for pose, K in zip(poses, Ks):
+            w2c = np.linalg.inv(pose)
+            out = dict(rgb=torch.empty((H, W, 3), device=dev), depth=torch.empty((H, W), device=dev),
+                       normal=torch.empty((H, W, 3), device=dev),
+                       mask=torch.empty((H, W), dtype=torch.uint8, device=dev),
+                       face_id=torch.empty((H, W), dtype=torch.int32, device=dev),
+                       bary=torch.empty((H, W, 3), device=dev), depth_z=torch.empty((H, W), device=dev))
+            counters = torch.empty(3, dtype=torch.int64, device=dev)
+            a = L.NrMeshRenderArgs()
+            a.verts, a.faces = v.data_ptr() if V else None, f.data_ptr() if F else None
+            a.normals = None if n is None or V == 0 else n.data_ptr()
+            a.colors = None if c is None or V == 0 else c.data_ptr()
+            a.V, a.F, a.H, a.W = V, F, H, W
+            a.w2c[:] = w2c[:3].reshape(-1).tolist()
+            a.m[:] = pose[:3, :3].reshape(-1).tolist()
+            a.fx, a.fy, a.cx, a.cy, a.skew = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]),
+                                              float(K[0, 1]))
+            a.near, a.large_threshold, a.ambient = float(near), lt, float(ambient)
+            a.base[:], a.background[:] = list(base), list(bg)
+            a.rgb, a.depth, a.normal = out['rgb'].data_ptr(), out['depth'].data_ptr(), out['normal'].data_ptr()
+            a.mask, a.face_id, a.bary = out['mask'].data_ptr(), out['face_id'].data_ptr(), out['bary'].data_ptr()
+            a.zdepth, a.counters = out['depth_z'].data_ptr(), counters.data_ptr()
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+            L.check(lib.nr_mesh_render(ctypes.byref(a), st))
+            out['mask'] = out['mask'].view(torch.bool)
+            out['n_clipped'], out['n_degenerate'], out['n_large'] = counters[0], counters[1], counters[2]
+            frames.append(out)
+    if not batched:
+        return frames[0]
+    return {k: torch.stack([fr[k] for fr in frames]) for k in frames[0]}
 
 
 def _have_skimage_and_plyfile():
