@@ -598,6 +598,62 @@ size_t nr_mesh_render_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W
 int nr_mesh_render(const NrMeshRenderArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh evaluation on the device: points on the surface (nr_meshsample.hip) and the exact nearest
+ * neighbour between two point clouds (nr_nn.hip), the two halves of the protocol NeuS, VolSDF and
+ * UNISURF are published against (accuracy / completeness / Chamfer distance of the extracted mesh to a
+ * ground-truth cloud, precision / recall / F-score at a threshold).  Every output is a pure function of
+ * the inputs, float64 with each operation rounded on its own: two runs are bit-identical and
+ * tests/mesh_metrics_ref.py restates both rules in numpy.  The rules in full, the order of the area
+ * sum and why the ring search stops exactly: the header comments of the two files.
+ *
+ * Sampler.  verts fp32 [V, 3], faces int32 [F, 3], 0 <= V, F <= INT32_MAX; u float64 [n, 3] in [0, 1).
+ *   nr_mesh_sample_workspace_bytes  12 bytes per 2048 faces (at least one slot), the two arrays rounded up
+ *                            to 256 bytes (0 on a bad count).
+ *   nr_mesh_face_cdf         cdf float64 [F]: the inclusive prefix sum of the face areas
+ *                            0.5 |e1 x e2| in an order fixed by F alone, non-decreasing; info (device
+ *                            float64 [2]) = {total = cdf[F - 1] (0 for F == 0), status}.  A face naming a
+ *                            vertex outside [0, V) is never dereferenced: area 0, status bit 0.  A non-finite
+ *                            area becomes 0: status bit 1.
+ *   nr_mesh_sample           sample k of n (0 <= n <= INT32_MAX), stratified: t = ((k + u[k,0]) / n) total,
+ *                            face = the first f with cdf[f] > t (binary search; past the end: the last face
+ *                            with cdf[f] > cdf[f - 1]), so a face of area 0 is never chosen; (a, b) =
+ *                            (u[k,1], u[k,2]), reflected to (1 - a, 1 - b) when a + b > 1, b0 = (1 - a) - b,
+ *                            p = (b0 v0 + a v1) + b v2 in float64, rounded once.  points fp32 [n, 3], face_id
+ *                            int32 [n]; with total == 0 every face_id is -1 and every point 0.
+ *
+ * Nearest neighbour.  points fp32 [N, 3], queries fp32 [M, 3], 0 <= N, M <= INT32_MAX.  Per pair
+ * d2 = (dx dx + dy dy) + dz dz in float64 from the widened coordinates; the neighbour is the point with
+ * the smallest (d2, index); kept iff d2 <= max_dist max_dist, else index -1 and d2 +inf.  Points with a
+ * non-finite coordinate are never neighbours; queries with one get -1 / +inf; so does every query when
+ * no finite point exists.
+ *   nr_nn_workspace_bytes    with C = max(1, min(4 N, 2^26)) cells at most: 256 + 2 x 4 (C + 1) + 4
+ *                            ceil((C + 1) / 1024) + 16 N + 4 M, each array rounded up to 256 bytes (0 on bad
+ *                            counts).  nr_nn_build needs nr_nn_workspace_bytes(N, 0) of it, nr_nn_bounds 256.
+ *   nr_nn_bounds             bounds (device float64 [8]) = {lo xyz, hi xyz of the finite points, 1 if there
+ *                            is one else 0, status}: what a caller needs to choose h.
+ *   nr_nn_build              uniform grid of cell size h (finite, > 0; doubled on the device until the
+ *                            grid has at most C cells) over the box of the finite points, and the points
+ *                            as 16-byte records (x, y, z, index) in cell order, in the workspace.
+ *   nr_nn_query              same N and workspace as the nr_nn_build before it (the records in the workspace
+ *                            carry the points).  max_dist >= 0,
+ *                            +inf for none.  index int32 [M], d2 float64 [M]; status (device int64 [1]):
+ *                            bit 0 a non-finite point was skipped; bit 1 the ring cap was reached (cannot
+ *                            happen; results unusable); bit 2 the workspace holds no build for this N
+ *                            (every query answered -1 / +inf).
+ * ------------------------------------------------------------------------------------------ */
+size_t nr_mesh_sample_workspace_bytes(int64_t F);
+int nr_mesh_face_cdf(const float* verts, int64_t V, const int32_t* faces, int64_t F, double* cdf, double* info,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int nr_mesh_sample(const float* verts, int64_t V, const int32_t* faces, int64_t F, const double* cdf, const double* u,
+                   int64_t n, float* points, int32_t* face_id, void* stream);
+size_t nr_nn_workspace_bytes(int64_t N, int64_t M);
+int nr_nn_bounds(const float* points, int64_t N, double* bounds, void* workspace, size_t workspace_bytes,
+                 void* stream);
+int nr_nn_build(const float* points, int64_t N, double h, void* workspace, size_t workspace_bytes, void* stream);
+int nr_nn_query(int64_t N, const float* queries, int64_t M, double max_dist, int32_t* index, double* d2,
+                int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training path (models/frameworks/neus.py:417-485, models/base.py:265-282 with
  * create_graph=True).  The host runs the step layer by layer: the dense [P, K] x [K, N] layer
  * products go to hipBLASLt, every per-point / per-ray step between them is one of these kernels.

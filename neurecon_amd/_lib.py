@@ -230,6 +230,14 @@ _SIGS = {
     # mesh rendering (nr_meshrender.hip)
     'nr_mesh_render_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     'nr_mesh_render': (_c_i, [ctypes.POINTER(NrMeshRenderArgs), _c_p]),
+    # mesh evaluation: surface samples (nr_meshsample.hip) and exact nearest neighbour (nr_nn.hip)
+    'nr_mesh_sample_workspace_bytes': (_c_sz, [_c_i64]),
+    'nr_mesh_face_cdf': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    'nr_mesh_sample': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    'nr_nn_workspace_bytes': (_c_sz, [_c_i64, _c_i64]),
+    'nr_nn_bounds': (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_sz, _c_p]),
+    'nr_nn_build': (_c_i, [_c_p, _c_i64, _c_d, _c_p, _c_sz, _c_p]),
+    'nr_nn_query': (_c_i, [_c_i64, _c_p, _c_i64, _c_d, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
     # training path (nr_train.hip)
     'nr_embed': (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_jvp': (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),

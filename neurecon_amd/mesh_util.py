@@ -40,6 +40,12 @@ samples exactly the pixels `rend_util.get_rays` shoots through, with the real pr
 overlays the volume-rendered frame of the same camera pixel for pixel.  A visibility-buffer rasteriser:
 exact integer coverage on vertices snapped to 1/256 pixel, the nearest face by a 64-bit atomic minimum of
 (depth bits, face index); every output is a pure function of the inputs.
+
+Measuring the result is `neurecon_amd.mesh_metrics`: `evaluate_mesh` samples the mesh's surface, searches the
+exact nearest neighbour against a ground-truth point cloud in both directions and returns accuracy,
+completeness, Chamfer distance and precision / recall / F-score, on the device (libnrhip `nr_mesh_face_cdf`,
+`nr_mesh_sample`, `nr_nn_build`, `nr_nn_query`); `read_ply_points` there reads the clouds `read_ply` refuses
+for having no faces.
 """
 import ctypes
 
