@@ -57,10 +57,23 @@ class ProfScope {
 // ---------------------------------------------------------------------------------------------
 // Exact-rounding fp32 arithmetic.  The reference runs eager fp32 PyTorch ops, i.e. every
 // mul/add is rounded separately; hipcc would otherwise contract a*b+c into one FMA.
+// The __f*_rn intrinsics do not prevent that: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers
+// define them as plain `x * y` / `x + y`, which carry the translation unit's contract flag and fuse
+// after inlining.  The contract(off) pragma takes the flag off these operations themselves, and it
+// stays off when they are inlined.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float fmul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float fadd(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float fsub(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ float fmul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float fadd(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float fsub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 __device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
 
 // ATen's CPU float sum of one contiguous row (cascade_sum -> vectorized_inner_sum, or row_sum for
@@ -75,9 +88,9 @@ __device__ float aten_row_sum(int n, Load ld) {
     const int si = n / 4;
     for (int i = 0; i < si; ++i)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) p[k] = __fadd_rn(p[k], ld(4 * i + k));
-    for (int t = si * 4; t < n; ++t) p[0] = __fadd_rn(p[0], ld(t));
-    return __fadd_rn(__fadd_rn(__fadd_rn(p[0], p[1]), p[2]), p[3]);
+      for (int k = 0; k < 4; ++k) p[k] = fadd(p[k], ld(4 * i + k));
+    for (int t = si * 4; t < n; ++t) p[0] = fadd(p[0], ld(t));
+    return fadd(fadd(fadd(p[0], p[1]), p[2]), p[3]);
   }
   const int vec_size = n / V, size_ilp = vec_size / 4;
   float acc[4][4][V];
@@ -97,14 +110,14 @@ __device__ float aten_row_sum(int n, Load ld) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int l = 0; l < V; ++l) acc[0][k][l] = __fadd_rn(acc[0][k][l], ld((4 * i + k) * V + l));
+        for (int l = 0; l < V; ++l) acc[0][k][l] = fadd(acc[0][k][l], ld((4 * i + k) * V + l));
 #pragma unroll
     for (int j = 1; j < 4; ++j) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int l = 0; l < V; ++l) {
-          acc[j][k][l] = __fadd_rn(acc[j][k][l], acc[j - 1][k][l]);
+          acc[j][k][l] = fadd(acc[j][k][l], acc[j - 1][k][l]);
           acc[j - 1][k][l] = 0.f;
         }
       if ((i & (mask << (j * lp))) != 0) break;
@@ -114,24 +127,24 @@ __device__ float aten_row_sum(int n, Load ld) {
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-      for (int l = 0; l < V; ++l) acc[0][k][l] = __fadd_rn(acc[0][k][l], ld((4 * i + k) * V + l));
+      for (int l = 0; l < V; ++l) acc[0][k][l] = fadd(acc[0][k][l], ld((4 * i + k) * V + l));
 #pragma unroll
   for (int j = 1; j < 4; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-      for (int l = 0; l < V; ++l) acc[0][k][l] = __fadd_rn(acc[0][k][l], acc[j][k][l]);
+      for (int l = 0; l < V; ++l) acc[0][k][l] = fadd(acc[0][k][l], acc[j][k][l]);
   for (int t = size_ilp * 4; t < vec_size; ++t)
 #pragma unroll
-    for (int l = 0; l < V; ++l) acc[0][0][l] = __fadd_rn(acc[0][0][l], ld(t * V + l));
+    for (int l = 0; l < V; ++l) acc[0][0][l] = fadd(acc[0][0][l], ld(t * V + l));
 #pragma unroll
   for (int k = 1; k < 4; ++k)
 #pragma unroll
-    for (int l = 0; l < V; ++l) acc[0][0][l] = __fadd_rn(acc[0][0][l], acc[0][k][l]);
+    for (int l = 0; l < V; ++l) acc[0][0][l] = fadd(acc[0][0][l], acc[0][k][l]);
   float fa = 0.f;
-  for (int t = vec_size * V; t < n; ++t) fa = __fadd_rn(fa, ld(t));
+  for (int t = vec_size * V; t < n; ++t) fa = fadd(fa, ld(t));
 #pragma unroll
-  for (int l = 0; l < V; ++l) fa = __fadd_rn(fa, acc[0][0][l]);
+  for (int l = 0; l < V; ++l) fa = fadd(fa, acc[0][0][l]);
   return fa;
 }
 

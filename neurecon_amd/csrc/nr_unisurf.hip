@@ -17,12 +17,22 @@ __device__ __forceinline__ float norm3f(float x, float y, float z) {
   return norm3_ref(x, y, z);
 }
 
+// OPT-OUT (NR_UNISURF_ROOT_FUSABLE): the root finder (near / far, the march, the secant steps and their
+// points) keeps arithmetic that the compiler may fuse into FMAs, as it was built before fmul / fadd / fsub
+// became exact.  Its result, the surface depth, is compared with the reference at the bar, never bit for
+// bit (eight secant steps on an SDF that itself differs by rounding), and the samples drawn from it below
+// use the exact helpers.  See DESIGN section 3 for why it is kept.
+__device__ __forceinline__ float rf_mul(float a, float b) { return a * b; }
+__device__ __forceinline__ float rf_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float rf_sub(float a, float b) { return a - b; }
+__device__ __forceinline__ float rf_lerp(float a, float b, float t) { return rf_add(rf_mul(a, rf_sub(1.0f, t)), rf_mul(b, t)); }
+
 // d_proposal = near * (1 - t) + far * t (ray_casting.py:79)
 __device__ __forceinline__ float lerp_ref(float a, float b, float t) { return fadd(fmul(a, fsub(1.0f, t)), fmul(b, t)); }
 
 // d_pred = -f_low * (d_high - d_low) / (f_high - f_low) + d_low (ray_casting.py:15, :29)
 __device__ __forceinline__ float secant(float d_lo, float f_lo, float d_hi, float f_hi) {
-  return fadd(fdiv(fmul(-f_lo, fsub(d_hi, d_lo)), fsub(f_hi, f_lo)), d_lo);
+  return rf_add(fdiv(rf_mul(-f_lo, rf_sub(d_hi, d_lo)), rf_sub(f_hi, f_lo)), d_lo);
 }
 
 enum { kDLo, kFLo, kDHi, kFHi, kDPred, kHit, kCross, kFree, kSec };
@@ -42,20 +52,20 @@ __global__ void uni_prologue(UniChunk c, const float* __restrict__ rays_o, const
   dz = fdiv(dz, nn);
   c.ro[r * 3 + 0] = ox; c.ro[r * 3 + 1] = oy; c.ro[r * 3 + 2] = oz;
   c.rd[r * 3 + 0] = dx; c.rd[r * 3 + 1] = dy; c.rd[r * 3 + 2] = dz;
-  const float mid = -fadd(fadd(fmul(ox, dx), fmul(oy, dy)), fmul(oz, dz));
-  float nr = fmaxf(fsub(mid, c.r_interest), 0.0f);
-  float fr = fmaxf(fadd(mid, c.r_interest), c.r_interest);
+  const float mid = -rf_add(rf_add(rf_mul(ox, dx), rf_mul(oy, dy)), rf_mul(oz, dz));
+  float nr = fmaxf(rf_sub(mid, c.r_interest), 0.0f);
+  float fr = fmaxf(rf_add(mid, c.r_interest), c.r_interest);
   if (!__builtin_isnan(c.near_bypass)) nr = c.near_bypass;
   if (!__builtin_isnan(c.far_bypass)) fr = c.far_bypass;
   c.near[r] = nr;
   c.far[r] = fr;
-  c.thr[r] = fadd(nr, fmul(fsub(fr, nr), c.too_close));
+  c.thr[r] = rf_add(nr, rf_mul(rf_sub(fr, nr), c.too_close));
   for (int i = 0; i < c.N_steps; ++i) {
-    const float d = lerp_ref(nr, fr, c.t_march[i]);
+    const float d = rf_lerp(nr, fr, c.t_march[i]);
     const int64_t q = (int64_t)i * c.R + r;
-    c.pts_m[q * 3 + 0] = fadd(ox, fmul(d, dx));
-    c.pts_m[q * 3 + 1] = fadd(oy, fmul(d, dy));
-    c.pts_m[q * 3 + 2] = fadd(oz, fmul(d, dz));
+    c.pts_m[q * 3 + 0] = rf_add(ox, rf_mul(d, dx));
+    c.pts_m[q * 3 + 1] = rf_add(oy, rf_mul(d, dy));
+    c.pts_m[q * 3 + 2] = rf_add(oz, rf_mul(d, dz));
   }
 }
 
@@ -75,12 +85,12 @@ __global__ void rf_prologue(UniChunk c, const float* __restrict__ rays_o, const 
   c.near[r] = near;
   c.far[r] = far;
   for (int i = 0; i < c.N_steps; ++i) {
-    const float d = lerp_ref(near, far, c.t_march[i]);
+    const float d = rf_lerp(near, far, c.t_march[i]);
     const int64_t q = (int64_t)i * c.R + r;
     // p_proposal = rays_o + d_proposal * rays_d (ray_casting.py:82)
-    c.pts_m[q * 3 + 0] = fadd(ox, fmul(d, dx));
-    c.pts_m[q * 3 + 1] = fadd(oy, fmul(d, dy));
-    c.pts_m[q * 3 + 2] = fadd(oz, fmul(d, dz));
+    c.pts_m[q * 3 + 0] = rf_add(ox, rf_mul(d, dx));
+    c.pts_m[q * 3 + 1] = rf_add(oy, rf_mul(d, dy));
+    c.pts_m[q * 3 + 2] = rf_add(oz, rf_mul(d, dz));
   }
 }
 
@@ -99,7 +109,7 @@ __global__ void rf_finish(UniChunk c, int64_t ray0, float* __restrict__ d_out, f
   const int64_t o = ray0 + r;
   d_out[o] = d;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) pts[o * 3 + k] = hit ? fadd(c.ro[r * 3 + k], fmul(dp, c.rd[r * 3 + k])) : 1.0f;
+  for (int k = 0; k < 3; ++k) pts[o * 3 + k] = hit ? rf_add(c.ro[r * 3 + k], rf_mul(dp, c.rd[r * 3 + k])) : 1.0f;
   mask[o] = hit ? 1 : 0;
   if (msc) msc[o] = s[kCross] != 0.0f ? 1 : 0;
 }
@@ -110,13 +120,13 @@ __global__ void uni_root(UniChunk c) {
   if (r >= c.R) return;
   const int N = c.N_steps;
   const float tau = c.logit_tau;
-  float v0 = fsub(c.sm[r], tau);
+  float v0 = rf_sub(c.sm[r], tau);
   const bool first_free = v0 > 0.0f;
   int idx = -1;
   float vi = v0, vn = 0.0f;
   for (int i = 0; i + 1 < N; ++i) {
-    vn = fsub(c.sm[(int64_t)(i + 1) * c.R + r], tau);
-    if (fmul(vi, vn) < 0.0f) {  // torch.sign(v_i * v_{i+1}) == -1: the earliest one wins the min
+    vn = rf_sub(c.sm[(int64_t)(i + 1) * c.R + r], tau);
+    if (rf_mul(vi, vn) < 0.0f) {  // torch.sign(v_i * v_{i+1}) == -1: the earliest one wins the min
       idx = i;
       break;
     }
@@ -132,15 +142,15 @@ __global__ void uni_root(UniChunk c) {
   if (hit) {
     const float nr = c.near[r], fr = c.far[r];
     const int i1 = idx + 1 < N ? idx + 1 : N - 1;
-    const float d_hi = lerp_ref(nr, fr, c.t_march[idx]), f_hi = vi;
-    const float d_lo = lerp_ref(nr, fr, c.t_march[i1]), f_lo = vn;
+    const float d_hi = rf_lerp(nr, fr, c.t_march[idx]), f_hi = vi;
+    const float d_lo = rf_lerp(nr, fr, c.t_march[i1]), f_lo = vn;
     s[kDLo] = d_lo; s[kFLo] = f_lo; s[kDHi] = d_hi; s[kFHi] = f_hi;
     if (!c.no_secant) dp = secant(d_lo, f_lo, d_hi, f_hi);
   }
   s[kDPred] = dp;
-  c.pts_s[r * 3 + 0] = fadd(c.ro[r * 3 + 0], fmul(dp, c.rd[r * 3 + 0]));
-  c.pts_s[r * 3 + 1] = fadd(c.ro[r * 3 + 1], fmul(dp, c.rd[r * 3 + 1]));
-  c.pts_s[r * 3 + 2] = fadd(c.ro[r * 3 + 2], fmul(dp, c.rd[r * 3 + 2]));
+  c.pts_s[r * 3 + 0] = rf_add(c.ro[r * 3 + 0], rf_mul(dp, c.rd[r * 3 + 0]));
+  c.pts_s[r * 3 + 1] = rf_add(c.ro[r * 3 + 1], rf_mul(dp, c.rd[r * 3 + 1]));
+  c.pts_s[r * 3 + 2] = rf_add(c.ro[r * 3 + 2], rf_mul(dp, c.rd[r * 3 + 2]));
 }
 
 // chunked march (kMarchK): after steps [s0, s1) are evaluated, the rays without a sign change among the
@@ -191,7 +201,7 @@ __global__ void uni_secant(UniChunk c, int last) {
   float* s = c.sec + (int64_t)r * kSec;
   if (s[kHit] == 0.0f) return;
   const float dp = s[kDPred];
-  const float fm = fsub(c.ss[r], c.logit_tau);
+  const float fm = rf_sub(c.ss[r], c.logit_tau);
   if (fm < 0.0f) {
     s[kDLo] = dp;
     s[kFLo] = fm;
@@ -202,9 +212,9 @@ __global__ void uni_secant(UniChunk c, int last) {
   const float dn = secant(s[kDLo], s[kFLo], s[kDHi], s[kFHi]);
   s[kDPred] = dn;
   if (!last) {
-    c.pts_s[r * 3 + 0] = fadd(c.ro[r * 3 + 0], fmul(dn, c.rd[r * 3 + 0]));
-    c.pts_s[r * 3 + 1] = fadd(c.ro[r * 3 + 1], fmul(dn, c.rd[r * 3 + 1]));
-    c.pts_s[r * 3 + 2] = fadd(c.ro[r * 3 + 2], fmul(dn, c.rd[r * 3 + 2]));
+    c.pts_s[r * 3 + 0] = rf_add(c.ro[r * 3 + 0], rf_mul(dn, c.rd[r * 3 + 0]));
+    c.pts_s[r * 3 + 1] = rf_add(c.ro[r * 3 + 1], rf_mul(dn, c.rd[r * 3 + 1]));
+    c.pts_s[r * 3 + 2] = rf_add(c.ro[r * 3 + 2], rf_mul(dn, c.rd[r * 3 + 2]));
   }
 }
 

@@ -79,7 +79,16 @@ class UNISURFOracle:
         t = torch.linspace(0.0, 1.0, steps=N_freespace)
         d_free = torch.ones([B, N, 1]) * near[..., None] * (1 - t) + d_lo.unsqueeze(-1) * t
         d_all = torch.sort(torch.cat([d_free, d_int], -1), -1)[0]
+        out = self.integrate(o, d, d_all, netchunk=netchunk, calc_normal=calc_normal, white_bkgd=white_bkgd)
+        out.update(surface_points=pt, mask_surface=hit, depth_surface=dpred)
+        return out
+
+    def integrate(self, o, d, d_all, netchunk=1048576, calc_normal=True, white_bkgd=False):
+        """unisurf.py:196-283 from given sorted sample depths d_all [B, N, P]; o, d [B, N, 3] with d
+        normalised: one ray chunk of the render loop (its points are the domain of the netchunk windows).
+        The arithmetic runs in the dtype of its inputs."""
         pts = o[..., None, :] + d[..., None, :] * d_all[..., :, None]
+        B, N = o.shape[:2]
         P = d_all.shape[-1]
         # batchify_query over flattened points (train_util.py:23-71): normalization domain = netchunk
         xf = pts.flatten(1, 2)
@@ -98,9 +107,8 @@ class UNISURFOracle:
         acc = torch.sum(w, -1)
         if white_bkgd:
             rgb = rgb + (1.0 - acc[..., None])
-        out = dict(rgb=rgb, depth_volume=depth, mask_volume=acc, surface_points=pt, mask_surface=hit,
-                   depth_surface=dpred, radiance=rad, implicit_surface=logits, implicit_nablas=nab,
-                   alpha=alpha, visibility_weights=w, d_all=d_all)
+        out = dict(rgb=rgb, depth_volume=depth, mask_volume=acc, radiance=rad, implicit_surface=logits,
+                   implicit_nablas=nab, alpha=alpha, visibility_weights=w, d_all=d_all)
         if calc_normal:
             nrm = F.normalize(nab, dim=-1)
             n = min(w.shape[-1], nrm.shape[-2])

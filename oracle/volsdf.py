@@ -159,6 +159,16 @@ class VolSDFOracle:
                                                   max_bisection=max_bisection_steps, N_final=N_importance,
                                                   N_up=N_samples * 4, perturb=perturb)
         d_all = torch.sort(torch.cat([d_coarse, d_fine], -1), -1)[0]
+        out = self.integrate(o, d, d_all, calc_normal=calc_normal, white_bkgd=white_bkgd, N_outside=N_outside,
+                             perturb=perturb)
+        out.update(beta_map=beta_map, iter_usage=usage)
+        return out
+
+    def integrate(self, o, d, d_all, calc_normal=True, white_bkgd=False, N_outside=32, perturb=False):
+        """volsdf.py:447-551 from given sorted sample depths d_all [B, N, S]; o, d [B, N, 3] with d
+        normalised.  The arithmetic runs in the dtype of its inputs (state dict, rays and depths alike)."""
+        B, N = o.shape[:2]
+        alpha, beta = self.forward_ab()
         pts = o[..., None, :] + d[..., None, :] * d_all[..., :, None]
         sdf, nablas, h = self.sdf_net.forward_with_nablas(pts)
         if self.nerf is None:
@@ -167,13 +177,13 @@ class VolSDFOracle:
         sigma = sdf_to_sigma(sdf, alpha, beta)
         extra = {}
         if self.nerf is not None:                                              # volsdf.py:451-469
-            t_out = torch.linspace(0, 1, N_outside + 2)[..., 1:-1].float()
+            t_out = torch.linspace(0, 1, N_outside + 2, dtype=torch.float32)[..., 1:-1].to(d_all.dtype)
             rs = (self.R / torch.flip(t_out, dims=[-1])).expand([B, N, N_outside])
             if perturb:                                                        # volsdf.py:460-465
                 mids = .5 * (rs[..., 1:] + rs[..., :-1])
                 upper = torch.cat([mids, rs[..., -1:]], -1)
                 lower = torch.cat([rs[..., :1], mids], -1)
-                rs = lower + (upper - lower) * torch.rand(upper.shape).float()
+                rs = lower + (upper - lower) * torch.rand(upper.shape).to(d_all.dtype)
             d_out = R.dvals_from_radius(o, d, rs)
             pts_out = o[..., None, :] + d[..., None, :] * d_out[..., :, None]
             x_out = torch.cat([pts_out / rs[..., None], 1. / rs[..., None]], dim=-1)
@@ -191,8 +201,7 @@ class VolSDFOracle:
         if white_bkgd:
             rgb = rgb + (1.0 - acc[..., None])
         out = dict(rgb=rgb, depth_volume=depth, mask_volume=acc, implicit_surface=sdf, implicit_nablas=nablas,
-                   radiance=rad, alpha=1.0 - p, p_i=p, visibility_weights=tau, d_vals=d_all, sigma=sigma,
-                   beta_map=beta_map, iter_usage=usage, **extra)
+                   radiance=rad, alpha=1.0 - p, p_i=p, visibility_weights=tau, d_vals=d_all, sigma=sigma, **extra)
         if calc_normal:
             nrm = F.normalize(nablas, dim=-1)
             n = min(tau.shape[-1], nrm.shape[-2])
