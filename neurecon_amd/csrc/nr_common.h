@@ -54,13 +54,35 @@ class ProfScope {
   size_t idx_ = 0;
 };
 
+// One timed launch: opens the kernel's ProfScope, launches, closes the scope; a launch error becomes
+// NR_ERR_HIP with its text, as NR_HIP_CHECK(hipGetLastError()) makes it.  Arguments convert to the
+// kernel's parameter types at the launch.
+template <class... P, class... A>
+int launch(const char* name, double units, void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, A... args) {
+  {
+    ProfScope prof(name, units, st);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  return NR_OK;
+}
+
+// nr::launch inside a function that returns the int status
+#define NR_LAUNCH(...)                                                                  \
+  do {                                                                                  \
+    const int _rc = ::nr::launch(__VA_ARGS__);                                          \
+    if (_rc) return _rc;                                                                \
+  } while (0)
+
 // ---------------------------------------------------------------------------------------------
-// Exact-rounding fp32 arithmetic.  The reference runs eager fp32 PyTorch ops, i.e. every
-// mul/add is rounded separately; hipcc would otherwise contract a*b+c into one FMA.
-// The __f*_rn intrinsics do not prevent that: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers
-// define them as plain `x * y` / `x + y`, which carry the translation unit's contract flag and fuse
-// after inlining.  The contract(off) pragma takes the flag off these operations themselves, and it
-// stays off when they are inlined.
+// Exact-rounding fp32 and fp64 arithmetic.  The reference runs eager fp32 PyTorch ops (and numpy
+// float64 ones), i.e. every mul/add is rounded separately; hipcc would otherwise contract a*b+c into
+// one FMA.  The __f*_rn intrinsics do not prevent that, and neither do __dmul_rn, __dadd_rn and
+// __dsub_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define them as plain `x * y` /
+// `x + y`, which carry the translation unit's contract flag and fuse after inlining.  The
+// contract(off) pragma takes the flag off these operations themselves, and it stays off when they
+// are inlined.  Exact arithmetic therefore goes through f* / d* below (or stands under a file-level
+// `#pragma clang fp contract(off)`), never through the __*_rn intrinsics.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float fmul(float a, float b) {
 #pragma clang fp contract(off)
@@ -75,6 +97,23 @@ __device__ __forceinline__ float fsub(float a, float b) {
   return a - b;
 }
 __device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
+
+__device__ __forceinline__ double dmul(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double dadd(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double dsub(double a, double b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ double ddiv(double a, double b) {  // IEEE: the expansion's own FMAs are part of it
+#pragma clang fp contract(off)
+  return a / b;
+}
 
 // ATen's CPU float sum of one contiguous row (cascade_sum -> vectorized_inner_sum, or row_sum for
 // rows shorter than a vector), reproduced operation for operation so that normalisers feeding a

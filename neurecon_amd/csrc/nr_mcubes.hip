@@ -15,8 +15,9 @@
 //   * Vertex position.  Edge from the point with index i along axis a, end values v0, v1:
 //     t = (level - v0) / (v1 - v0) in float64 from the fp32 inputs (never 0/0: the ends differ in
 //     class); the index-space coordinate is i + t on axis a and the integer index on the other two;
-//     pos = ((idx * spacing + origin) / scale) - offset per axis in float64 (every operation rounded
-//     on its own, no contraction), rounded to fp32 once.
+//     pos = ((idx * spacing + origin) / scale) - offset per axis in float64, every operation rounded on
+//     its own (dmul / dadd / ddiv / dsub of nr_common.h: the product and the sum are never contracted
+//     into a fused multiply-add), rounded to fp32 once.
 //   * Orientation.  With output axes 0, 1, 2 read as a right-handed x, y, z, triangle normals
 //     (right-hand rule on the emitted vertex order) point toward larger volume values: outward for an
 //     SDF, and a closed surface has positive signed volume.
@@ -57,7 +58,7 @@
 // Flat indices are 64 bit throughout; V and F must fit int32 (PLY `int`).
 #include <mutex>
 
-#include "nr_common.h"
+#include "nr_meshcommon.h"
 
 namespace nr {
 
@@ -250,23 +251,6 @@ __device__ __forceinline__ void mc_coords(const McDims& d, int64_t p, int64_t& i
   }
 }
 
-// sum of `mine` over the workgroup's earlier waves; total over all waves in `all` (LDS, 4 waves)
-__device__ __forceinline__ int mc_wave_prefix(int mine, int* lds, int& all) {
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds[wave] = mine;
-  __syncthreads();
-  int pre = 0;
-  all = 0;
-#pragma unroll
-  for (int w = 0; w < kMcWG / 64; ++w) {
-    const int v = lds[w];
-    pre += w < wave ? v : 0;
-    all += v;
-  }
-  __syncthreads();
-  return pre;
-}
-
 // the 8 corner classes of the cell at p (which must have all its corners inside the grid)
 __device__ __forceinline__ unsigned mc_case(const float* __restrict__ vol, const McDims& d, int64_t p, float level) {
   const int64_t s0 = d.n1 * d.n2, s1 = d.n2;
@@ -306,50 +290,29 @@ __global__ __launch_bounds__(kMcWG) void mc_classify(const float* __restrict__ v
     nt += __popcll(__ballot((code >> (3 + b)) & 1u)) << b;
   }
   int all_v, all_t;
-  mc_wave_prefix(nv, lds, all_v);
-  mc_wave_prefix(nt, lds, all_t);
+  wave_prefix<kMcWG>(nv, lds, all_v);
+  wave_prefix<kMcWG>(nt, lds, all_t);
   if (threadIdx.x == 0) wgsum[blockIdx.x] = make_int2(all_v, all_t);
 }
 
-// in place: wgsum[b] = {vertices, triangles} before workgroup b; totals = {V, F}.  One workgroup; thread
-// t owns a contiguous strip of workgroups.  The int32 bases are meaningful only while V, F fit int32
-// (the caller checks the int64 totals before it emits).
+struct McSum {  // the scan's accumulator: {vertices, triangles}, 64 bit
+  int64_t v, f;
+  __device__ McSum& operator+=(const McSum& o) { return v += o.v, f += o.f, *this; }
+  __device__ McSum operator-(const McSum& o) const { return {v - o.v, f - o.f}; }
+};
+
+// in place: wgsum[b] = {vertices, triangles} before workgroup b; totals = {V, F}.  One workgroup
+// (strip_scan).  The int32 bases are meaningful only while V, F fit int32 (the caller checks the int64
+// totals before it emits).
 __global__ __launch_bounds__(kMcScanWG) void mc_scan(int2* __restrict__ wgsum, int64_t nb, int64_t* __restrict__ totals) {
-  __shared__ int64_t sv[kMcScanWG], sf[kMcScanWG];
-  const int tid = threadIdx.x;
-  const int64_t L = (nb + kMcScanWG - 1) / kMcScanWG;
-  const int64_t lo = tid * L, hi = lo + L < nb ? lo + L : nb;
-  int64_t a = 0, b = 0;
-  for (int64_t q = lo; q < hi; ++q) {
+  __shared__ McSum s[kMcScanWG];
+  const auto get = [&](int64_t q) {
     const int2 c = wgsum[q];
-    a += c.x;
-    b += c.y;
-  }
-  sv[tid] = a;
-  sf[tid] = b;
-  __syncthreads();
-  for (int off = 1; off < kMcScanWG; off <<= 1) {
-    int64_t x = 0, y = 0;
-    if (tid >= off) {
-      x = sv[tid - off];
-      y = sf[tid - off];
-    }
-    __syncthreads();
-    sv[tid] += x;
-    sf[tid] += y;
-    __syncthreads();
-  }
-  int64_t ea = sv[tid] - a, eb = sf[tid] - b;
-  for (int64_t q = lo; q < hi; ++q) {
-    const int2 c = wgsum[q];
-    wgsum[q] = make_int2((int)ea, (int)eb);
-    ea += c.x;
-    eb += c.y;
-  }
-  if (tid == kMcScanWG - 1) {
-    totals[0] = sv[tid];
-    totals[1] = sf[tid];
-  }
+    return McSum{c.x, c.y};
+  };
+  const auto put = [&](int64_t q, const McSum& e) { wgsum[q] = make_int2((int)e.v, (int)e.f); };
+  const McSum all = strip_scan<kMcScanWG>(nb, s, get, put);
+  if (threadIdx.x == kMcScanWG - 1) totals[0] = all.v, totals[1] = all.f;
 }
 
 __global__ __launch_bounds__(kMcWG) void mc_verts(const float* __restrict__ vol, McDims d, float level, McXf xf,
@@ -367,7 +330,7 @@ __global__ __launch_bounds__(kMcWG) void mc_verts(const float* __restrict__ vol,
     wave_total += __popcll(m);
   }
   int all;
-  const int64_t first = (int64_t)wgbase[blockIdx.x].x + mc_wave_prefix(wave_total, lds, all) + rank;
+  const int64_t first = (int64_t)wgbase[blockIdx.x].x + wave_prefix<kMcWG>(wave_total, lds, all) + rank;
   if (p >= d.n) return;
   voff[p] = (int)first;
   if (f == 0) return;
@@ -380,13 +343,13 @@ __global__ __launch_bounds__(kMcWG) void mc_verts(const float* __restrict__ vol,
   for (int a = 0; a < 3; ++a) {
     if (!((f >> a) & 1u) || ijk[a] + 1 >= dims[a]) continue;
     const double v1 = (double)vol[p + stride[a]];
-    const double t = __ddiv_rn(__dsub_rn(lv, v0), __dsub_rn(v1, v0));
+    const double t = ddiv(dsub(lv, v0), dsub(v1, v0));
     if (slot < n_verts) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const double idx = c == a ? __dadd_rn((double)ijk[c], t) : (double)ijk[c];
-        const double w = __ddiv_rn(__dadd_rn(__dmul_rn(idx, xf.spacing[c]), xf.origin[c]), xf.scale);
-        verts[slot * 3 + c] = (float)__dsub_rn(w, xf.offset[c]);
+        const double idx = c == a ? dadd((double)ijk[c], t) : (double)ijk[c];
+        const double w = ddiv(dadd(dmul(idx, xf.spacing[c]), xf.origin[c]), xf.scale);
+        verts[slot * 3 + c] = (float)dsub(w, xf.offset[c]);
       }
     }
     ++slot;
@@ -408,7 +371,7 @@ __global__ __launch_bounds__(kMcWG) void mc_faces(const float* __restrict__ vol,
     wave_total += __popcll(m) << b;
   }
   int all;
-  const int64_t first = (int64_t)wgbase[blockIdx.x].y + mc_wave_prefix(wave_total, lds, all) + rank;
+  const int64_t first = (int64_t)wgbase[blockIdx.x].y + wave_prefix<kMcWG>(wave_total, lds, all) + rank;
   if (nt == 0) return;
   int64_t i, j, k;
   mc_coords(d, p, i, j, k);
@@ -437,8 +400,6 @@ __global__ __launch_bounds__(kMcWG) void mc_faces(const float* __restrict__ vol,
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static size_t mc_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 constexpr int64_t kMcMaxDim = (int64_t)1 << 30;
 constexpr int64_t kMcMaxPoints = (int64_t)1 << 38;  // 2^30 workgroups
 
@@ -454,9 +415,9 @@ static bool mc_plan(int64_t n0, int64_t n1, int64_t n2, McPlan& p) {
   p.d = McDims{n0, n1, n2, n0 * n1 * n2};
   p.nb = (p.d.n + kMcWG - 1) / kMcWG;
   size_t o = 0;
-  p.o_codes = o; o += mc_a256((size_t)p.d.n);
-  p.o_voff = o; o += mc_a256((size_t)p.d.n * 4);
-  p.o_wg = o; o += mc_a256((size_t)p.nb * 8);
+  p.o_codes = o; o += a256((size_t)p.d.n);
+  p.o_voff = o; o += a256((size_t)p.d.n * 4);
+  p.o_wg = o; o += a256((size_t)p.nb * 8);
   p.total = o;
   return true;
 }
@@ -510,17 +471,9 @@ int nr_mc_count(const float* volume, int64_t n0, int64_t n1, int64_t n2, float l
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   int2* wg = (int2*)(ws + pl.o_wg);
-  {
-    ProfScope prof("mc_classify", (double)pl.d.n, st);
-    hipLaunchKernelGGL(mc_classify, dim3((unsigned)pl.nb), dim3(kMcWG), 0, st, volume, pl.d, level,
-                       (uint8_t*)(ws + pl.o_codes), wg);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  {
-    ProfScope prof("mc_scan", (double)pl.nb, st);
-    hipLaunchKernelGGL(mc_scan, dim3(1), dim3(kMcScanWG), 0, st, wg, pl.nb, totals);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("mc_classify", (double)pl.d.n, mc_classify, dim3((unsigned)pl.nb), dim3(kMcWG), st, volume, pl.d, level,
+            (uint8_t*)(ws + pl.o_codes), wg);
+  NR_LAUNCH("mc_scan", (double)pl.nb, mc_scan, dim3(1), dim3(kMcScanWG), st, wg, pl.nb, totals);
   return NR_OK;
 }
 
@@ -549,18 +502,10 @@ int nr_mc_emit(const float* volume, int64_t n0, int64_t n1, int64_t n2, float le
   McXf xf;
   for (int c = 0; c < 3; ++c) xf.spacing[c] = spacing[c], xf.origin[c] = origin[c], xf.offset[c] = offset[c];
   xf.scale = scale;
-  {
-    ProfScope prof("mc_verts", (double)pl.d.n, st);
-    hipLaunchKernelGGL(mc_verts, dim3((unsigned)pl.nb), dim3(kMcWG), 0, st, volume, pl.d, level, xf, codes, wg, voff,
-                       verts, n_verts);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  {
-    ProfScope prof("mc_faces", (double)pl.d.n, st);
-    hipLaunchKernelGGL(mc_faces, dim3((unsigned)pl.nb), dim3(kMcWG), 0, st, volume, pl.d, level, codes, wg, voff,
-                       faces, n_faces);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("mc_verts", (double)pl.d.n, mc_verts, dim3((unsigned)pl.nb), dim3(kMcWG), st, volume, pl.d, level, xf, codes,
+            wg, voff, verts, n_verts);
+  NR_LAUNCH("mc_faces", (double)pl.d.n, mc_faces, dim3((unsigned)pl.nb), dim3(kMcWG), st, volume, pl.d, level, codes, wg,
+            voff, faces, n_faces);
   return NR_OK;
 }
 

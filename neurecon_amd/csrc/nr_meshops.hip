@@ -55,7 +55,7 @@
 //             dropped vertex); faces (next launch): the same rank for faces, indices through new[].
 // Workspace: 256 header bytes + 4 bytes per vertex (parent, reused as new[]) + 4 bytes per 256
 // vertices + 4 bytes per 256 faces, each array rounded up to 256 bytes.
-#include "nr_common.h"
+#include "nr_meshcommon.h"
 
 namespace nr {
 
@@ -100,10 +100,6 @@ __device__ __forceinline__ bool mo_unite(int* __restrict__ parent, int u, int v,
   }
 }
 
-__device__ __forceinline__ bool mo_valid(int a, int b, int c, int64_t V) {
-  return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
-}
-
 __global__ __launch_bounds__(kMoWG) void mo_init(int* __restrict__ parent, int* __restrict__ face_count, int64_t V,
                                                  MoHeader* __restrict__ hdr) {
   const int64_t v = (int64_t)blockIdx.x * kMoWG + threadIdx.x;
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(kMoWG) void mo_hook(const int* __restrict__ faces, 
   const int64_t f = (int64_t)blockIdx.x * kMoWG + threadIdx.x;
   if (f >= F) return;
   const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-  if (!mo_valid(a, b, c, V)) {
+  if (!face_valid(a, b, c, V)) {
     atomicOr(&hdr->status, (unsigned)kMoBadIndex);
     return;
   }
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(kMoWG) void mo_count(const int* __restrict__ faces,
   int label = -1;
   if (f < F) {
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (mo_valid(a, b, c, V)) label = labels[a];
+    if (face_valid(a, b, c, V)) label = labels[a];
   }
   // one add per distinct label of the wave (at most 64 rounds, all inside the wave)
   const int lane = threadIdx.x & 63;
@@ -197,28 +193,11 @@ __global__ void mo_finish(const MoHeader* __restrict__ hdr, int64_t* __restrict_
   totals[3] = (int64_t)hdr->status;
 }
 
-// sum of `mine` over the workgroup's earlier waves; total over all waves in `all`
-__device__ __forceinline__ int mo_wave_prefix(int mine, int* lds, int& all) {
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds[wave] = mine;
-  __syncthreads();
-  int pre = 0;
-  all = 0;
-#pragma unroll
-  for (int w = 0; w < kMoWG / 64; ++w) {
-    const int x = lds[w];
-    pre += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();
-  return pre;
-}
-
 __device__ __forceinline__ bool mo_face_kept(const int* __restrict__ faces, int64_t f, int64_t F, int64_t V,
                                              const uint8_t* __restrict__ vkeep, int& a, int& b, int& c) {
   if (f >= F) return false;
   a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-  return mo_valid(a, b, c, V) && vkeep[a] && vkeep[b] && vkeep[c];
+  return face_valid(a, b, c, V) && vkeep[a] && vkeep[b] && vkeep[c];
 }
 
 // workgroups [0, nbv): vertices; [nbv, nbv + nbf): faces
@@ -237,7 +216,7 @@ __global__ __launch_bounds__(kMoWG) void mo_filter_count(const int* __restrict__
     keep = i < V && vkeep[i];
   }
   int all;
-  mo_wave_prefix(__popcll(__ballot(keep)), lds, all);
+  wave_prefix<kMoWG>(__popcll(__ballot(keep)), lds, all);
   if (threadIdx.x == 0) (is_face ? wf : wv)[blk] = all;
 }
 
@@ -248,26 +227,9 @@ __global__ __launch_bounds__(kMoScanWG) void mo_scan(int* __restrict__ wv, int64
   __shared__ int64_t s[kMoScanWG];
   int* __restrict__ w = blockIdx.x == 0 ? wv : wf;
   const int64_t nb = blockIdx.x == 0 ? nbv : nbf;
-  const int tid = threadIdx.x;
-  const int64_t L = (nb + kMoScanWG - 1) / kMoScanWG;
-  const int64_t lo = tid * L < nb ? tid * L : nb, hi = lo + L < nb ? lo + L : nb;
-  int64_t a = 0;
-  for (int64_t q = lo; q < hi; ++q) a += w[q];
-  s[tid] = a;
-  __syncthreads();
-  for (int off = 1; off < kMoScanWG; off <<= 1) {
-    const int64_t x = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += x;
-    __syncthreads();
-  }
-  int64_t e = s[tid] - a;
-  for (int64_t q = lo; q < hi; ++q) {
-    const int c = w[q];
-    w[q] = (int)e;
-    e += c;
-  }
-  if (tid == kMoScanWG - 1) totals[blockIdx.x] = s[tid];
+  const int64_t all = strip_scan<kMoScanWG>(nb, s, [&](int64_t q) { return (int64_t)w[q]; },
+                                            [&](int64_t q, int64_t e) { w[q] = (int)e; });
+  if (threadIdx.x == kMoScanWG - 1) totals[blockIdx.x] = all;
 }
 
 __global__ __launch_bounds__(kMoWG) void mo_emit_verts(const uint8_t* __restrict__ vkeep, int64_t V,
@@ -279,7 +241,7 @@ __global__ __launch_bounds__(kMoWG) void mo_emit_verts(const uint8_t* __restrict
   const unsigned long long m = __ballot(keep);
   const unsigned long long lt = (1ull << (threadIdx.x & 63)) - 1ull;
   int all;
-  const int64_t slot = (int64_t)wv[blockIdx.x] + mo_wave_prefix(__popcll(m), lds, all) + __popcll(m & lt);
+  const int64_t slot = (int64_t)wv[blockIdx.x] + wave_prefix<kMoWG>(__popcll(m), lds, all) + __popcll(m & lt);
   if (v >= V) return;
   const bool store = keep && slot < Vk;
   vnew[v] = store ? (int)slot : -1;
@@ -297,7 +259,7 @@ __global__ __launch_bounds__(kMoWG) void mo_emit_faces(const int* __restrict__ f
   const unsigned long long m = __ballot(keep);
   const unsigned long long lt = (1ull << (threadIdx.x & 63)) - 1ull;
   int all;
-  const int64_t slot = (int64_t)wf[blockIdx.x] + mo_wave_prefix(__popcll(m), lds, all) + __popcll(m & lt);
+  const int64_t slot = (int64_t)wf[blockIdx.x] + wave_prefix<kMoWG>(__popcll(m), lds, all) + __popcll(m & lt);
   if (!keep || slot >= Fk) return;
   faces_out[3 * slot] = vnew[a];
   faces_out[3 * slot + 1] = vnew[b];
@@ -307,8 +269,6 @@ __global__ __launch_bounds__(kMoWG) void mo_emit_faces(const int* __restrict__ f
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static size_t mo_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct MoPlan {
   int64_t nbv, nbf;
   size_t o_idx, o_wv, o_wf, total;
@@ -319,9 +279,9 @@ static bool mo_plan(int64_t V, int64_t F, MoPlan& p) {
   p.nbv = (V + kMoWG - 1) / kMoWG;
   p.nbf = (F + kMoWG - 1) / kMoWG;
   size_t o = 256;  // MoHeader
-  p.o_idx = o; o += mo_a256((size_t)V * 4);
-  p.o_wv = o; o += mo_a256((size_t)p.nbv * 4);
-  p.o_wf = o; o += mo_a256((size_t)p.nbf * 4);
+  p.o_idx = o; o += a256((size_t)V * 4);
+  p.o_wv = o; o += a256((size_t)p.nbv * 4);
+  p.o_wf = o; o += a256((size_t)p.nbf * 4);
   p.total = o;
   return true;
 }
@@ -349,31 +309,12 @@ int nr_mesh_components(const int32_t* faces, int64_t F, int64_t V, int32_t* labe
   MoHeader* hdr = (MoHeader*)ws;
   int* parent = (int*)(ws + pl.o_idx);
   const unsigned gv = (unsigned)(pl.nbv > 0 ? pl.nbv : 1), gf = (unsigned)pl.nbf;
-  {
-    ProfScope prof("mesh_init", (double)V, st);
-    hipLaunchKernelGGL(mo_init, dim3(gv), dim3(kMoWG), 0, st, parent, face_count, V, hdr);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  if (F > 0) {
-    ProfScope prof("mesh_hook", (double)F, st);
-    hipLaunchKernelGGL(mo_hook, dim3(gf), dim3(kMoWG), 0, st, faces, F, V, parent, hdr, 2 * V + 64);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  if (V > 0) {
-    ProfScope prof("mesh_flatten", (double)V, st);
-    hipLaunchKernelGGL(mo_flatten, dim3(gv), dim3(kMoWG), 0, st, parent, labels, V, hdr);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  if (F > 0 && V > 0) {
-    ProfScope prof("mesh_count", (double)F, st);
-    hipLaunchKernelGGL(mo_count, dim3(gf), dim3(kMoWG), 0, st, faces, F, V, labels, face_count);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  if (V > 0) {
-    ProfScope prof("mesh_reduce", (double)V, st);
-    hipLaunchKernelGGL(mo_reduce, dim3(gv), dim3(kMoWG), 0, st, labels, face_count, V, hdr);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("mesh_init", (double)V, mo_init, dim3(gv), dim3(kMoWG), st, parent, face_count, V, hdr);
+  if (F > 0) NR_LAUNCH("mesh_hook", (double)F, mo_hook, dim3(gf), dim3(kMoWG), st, faces, F, V, parent, hdr, 2 * V + 64);
+  if (V > 0) NR_LAUNCH("mesh_flatten", (double)V, mo_flatten, dim3(gv), dim3(kMoWG), st, parent, labels, V, hdr);
+  if (F > 0 && V > 0)
+    NR_LAUNCH("mesh_count", (double)F, mo_count, dim3(gf), dim3(kMoWG), st, faces, F, V, labels, face_count);
+  if (V > 0) NR_LAUNCH("mesh_reduce", (double)V, mo_reduce, dim3(gv), dim3(kMoWG), st, labels, face_count, V, hdr);
   hipLaunchKernelGGL(mo_finish, dim3(1), dim3(64), 0, st, hdr, totals);
   NR_HIP_CHECK(hipGetLastError());
   return NR_OK;
@@ -388,17 +329,10 @@ int nr_mesh_filter_count(const int32_t* faces, int64_t F, int64_t V, const uint8
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   int *wv = (int*)(ws + pl.o_wv), *wf = (int*)(ws + pl.o_wf);
-  if (pl.nbv + pl.nbf > 0) {
-    ProfScope prof("mesh_filter_count", (double)(V + F), st);
-    hipLaunchKernelGGL(mo_filter_count, dim3((unsigned)(pl.nbv + pl.nbf)), dim3(kMoWG), 0, st, faces, F, V, vkeep,
-                       pl.nbv, wv, wf);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  {
-    ProfScope prof("mesh_scan", (double)(pl.nbv + pl.nbf), st);
-    hipLaunchKernelGGL(mo_scan, dim3(2), dim3(kMoScanWG), 0, st, wv, pl.nbv, wf, pl.nbf, totals);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  if (pl.nbv + pl.nbf > 0)
+    NR_LAUNCH("mesh_filter_count", (double)(V + F), mo_filter_count, dim3((unsigned)(pl.nbv + pl.nbf)), dim3(kMoWG), st,
+              faces, F, V, vkeep, pl.nbv, wv, wf);
+  NR_LAUNCH("mesh_scan", (double)(pl.nbv + pl.nbf), mo_scan, dim3(2), dim3(kMoScanWG), st, wv, pl.nbv, wf, pl.nbf, totals);
   return NR_OK;
 }
 
@@ -419,17 +353,12 @@ int nr_mesh_filter_emit(const int32_t* faces, int64_t F, int64_t V, const uint8_
   char* ws = (char*)workspace;
   int* vnew = (int*)(ws + pl.o_idx);
   const int *wv = (const int*)(ws + pl.o_wv), *wf = (const int*)(ws + pl.o_wf);
-  if (V > 0) {
-    ProfScope prof("mesh_emit_verts", (double)V, st);
-    hipLaunchKernelGGL(mo_emit_verts, dim3((unsigned)pl.nbv), dim3(kMoWG), 0, st, vkeep, V, wv, vnew, vsrc, Vk);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  if (Fk > 0) {
-    ProfScope prof("mesh_emit_faces", (double)F, st);
-    hipLaunchKernelGGL(mo_emit_faces, dim3((unsigned)pl.nbf), dim3(kMoWG), 0, st, faces, F, V, vkeep, wf, vnew,
-                       faces_out, Fk);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  if (V > 0)
+    NR_LAUNCH("mesh_emit_verts", (double)V, mo_emit_verts, dim3((unsigned)pl.nbv), dim3(kMoWG), st, vkeep, V, wv, vnew,
+              vsrc, Vk);
+  if (Fk > 0)
+    NR_LAUNCH("mesh_emit_faces", (double)F, mo_emit_faces, dim3((unsigned)pl.nbf), dim3(kMoWG), st, faces, F, V, vkeep,
+              wf, vnew, faces_out, Fk);
   return NR_OK;
 }
 

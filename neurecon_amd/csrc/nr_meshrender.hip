@@ -7,11 +7,9 @@
 //
 // Every output is a pure function of the inputs: two runs are bit-identical, and permuting the faces
 // changes only the ids.  All arithmetic below is float64 with each operation rounded on its own, or exact
-// integer.  What forbids contraction into fused multiply-adds is the `#pragma clang fp contract(off)` below
-// the includes together with mr_mul / mr_add / mr_dif / mr_div, plain operators written under it.  The HIP
-// header's __dmul_rn / __dadd_rn / __dsub_rn would not do: in this toolchain they are plain * + - defined in
-// a header that is parsed before any pragma of this file, so their results stay contractable after inlining.
-// With the pragma the two rasteriser paths cannot differ by a fusion and a toolchain's contraction choices
+// integer.  What forbids contraction into fused multiply-adds is dmul / dadd / dsub / ddiv (nr_common.h, which
+// also says why the __d*_rn intrinsics would not do) together with the `#pragma clang fp contract(off)` below
+// the includes.  The two rasteriser paths cannot differ by a fusion and a toolchain's contraction choices
 // cannot reach the outputs; the file's fused multiply-add count equals that of a -ffp-contract=off build
 // (what is left are the expansions of the float64 division and square root, which are correctly rounded).
 //
@@ -76,7 +74,7 @@
 // Kernels: mr_setup (vertex stage + key clear), mr_faces (bin + small path), mr_large (queued faces),
 // mr_resolve.  Workspace: 256 header bytes + 8 bytes per vertex (X, Y) + 24 per vertex (p_c) + 8 per pixel
 // (keys) + 4 per face (queue), each array rounded up to 256 bytes.
-#include "nr_common.h"
+#include "nr_meshcommon.h"
 
 #pragma clang fp contract(off)  // no a * b + c -> fma anywhere in this file (header comment)
 
@@ -99,14 +97,8 @@ struct MrCam {
   int H, W;
 };
 
-// one IEEE operation each, never fused with a neighbour (the pragma above)
-__device__ __forceinline__ double mr_mul(double a, double b) { return a * b; }
-__device__ __forceinline__ double mr_add(double a, double b) { return a + b; }
-__device__ __forceinline__ double mr_dif(double a, double b) { return a - b; }
-__device__ __forceinline__ double mr_div(double a, double b) { return a / b; }
-
 __device__ __forceinline__ double mr_dot3(double ax, double ay, double az, double bx, double by, double bz) {
-  return mr_add(mr_add(mr_mul(ax, bx), mr_mul(ay, by)), mr_mul(az, bz));
+  return dadd(dadd(dmul(ax, bx), dmul(ay, by)), dmul(az, bz));
 }
 
 struct MrVec {
@@ -114,21 +106,21 @@ struct MrVec {
 };
 
 __device__ __forceinline__ MrVec mr_sub(const MrVec& a, const MrVec& b) {
-  return {mr_dif(a.x, b.x), mr_dif(a.y, b.y), mr_dif(a.z, b.z)};
+  return {dsub(a.x, b.x), dsub(a.y, b.y), dsub(a.z, b.z)};
 }
 
 __device__ __forceinline__ MrVec mr_cross(const MrVec& a, const MrVec& b) {
-  return {mr_dif(mr_mul(a.y, b.z), mr_mul(a.z, b.y)), mr_dif(mr_mul(a.z, b.x), mr_mul(a.x, b.z)),
-          mr_dif(mr_mul(a.x, b.y), mr_mul(a.y, b.x))};
+  return {dsub(dmul(a.y, b.z), dmul(a.z, b.y)), dsub(dmul(a.z, b.x), dmul(a.x, b.z)),
+          dsub(dmul(a.x, b.y), dmul(a.y, b.x))};
 }
 
 __device__ __forceinline__ double mr_dot(const MrVec& a, const MrVec& b) { return mr_dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 
 // ray(i, j): `lift` in float64
 __device__ __forceinline__ void mr_ray(const MrCam& c, int i, int j, double& xl, double& yl) {
-  const double a = mr_add(mr_dif((double)i, c.cx), mr_div(mr_mul(c.cy, c.sk), c.fy));
-  xl = mr_div(mr_dif(a, mr_div(mr_mul(c.sk, (double)j), c.fy)), c.fx);
-  yl = mr_div(mr_dif((double)j, c.cy), c.fy);
+  const double a = dadd(dsub((double)i, c.cx), ddiv(dmul(c.cy, c.sk), c.fy));
+  xl = ddiv(dsub(a, ddiv(dmul(c.sk, (double)j), c.fy)), c.fx);
+  yl = ddiv(dsub((double)j, c.cy), c.fy);
 }
 
 // the depth plane of a face: n and num from the camera-space vertices in stored order
@@ -150,13 +142,9 @@ __device__ __forceinline__ MrPlane mr_plane(const double* __restrict__ pc, int a
 }
 
 __device__ __forceinline__ bool mr_tz(const MrPlane& p, double xl, double yl, double& t) {
-  const double den = mr_add(mr_add(mr_mul(p.n.x, xl), mr_mul(p.n.y, yl)), p.n.z);
-  t = mr_div(p.num, den);
+  const double den = dadd(dadd(dmul(p.n.x, xl), dmul(p.n.y, yl)), p.n.z);
+  t = ddiv(p.num, den);
   return isfinite(t) && t > 0.0;
-}
-
-__device__ __forceinline__ bool mr_valid(int a, int b, int c, int64_t V) {
-  return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
 }
 
 // floor(x / 256) and ceil(x / 256) of a possibly negative int
@@ -198,7 +186,7 @@ enum { kMrSkip = 0, kMrClipped = 1, kMrDegenerate = 2, kMrDraw = 3 };
 __device__ __forceinline__ int mr_face(const int* __restrict__ faces, int64_t f, int64_t V, const int2* __restrict__ xy,
                                        int H, int W, int& a, int& b, int& c, MrTri& t) {
   a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-  if (!mr_valid(a, b, c, V)) return kMrDegenerate;
+  if (!face_valid(a, b, c, V)) return kMrDegenerate;
   const int2 p0 = xy[a], p1 = xy[b], p2 = xy[c];
   if (p0.x == kMrFlag || p1.x == kMrFlag || p2.x == kMrFlag) return kMrClipped;
   const int64_t a2 = ((int64_t)p1.x - p0.x) * ((int64_t)p2.y - p0.y) - ((int64_t)p1.y - p0.y) * ((int64_t)p2.x - p0.x);
@@ -230,17 +218,17 @@ __global__ __launch_bounds__(kMrWG) void mr_setup(const float* __restrict__ vert
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double* w = cam.w2c + 4 * k;
-    p[k] = mr_add(mr_add(mr_add(mr_mul(w[0], x), mr_mul(w[1], y)), mr_mul(w[2], z)), w[3]);
+    p[k] = dadd(dadd(dadd(dmul(w[0], x), dmul(w[1], y)), dmul(w[2], z)), w[3]);
     pc[3 * t + k] = p[k];
   }
-  const double xp = mr_div(p[0], p[2]), yp = mr_div(p[1], p[2]);
-  const double u = mr_add(mr_add(mr_mul(cam.fx, xp), mr_mul(cam.sk, yp)), cam.cx);
-  const double v = mr_add(mr_mul(cam.fy, yp), cam.cy);
+  const double xp = ddiv(p[0], p[2]), yp = ddiv(p[1], p[2]);
+  const double u = dadd(dadd(dmul(cam.fx, xp), dmul(cam.sk, yp)), cam.cx);
+  const double v = dadd(dmul(cam.fy, yp), cam.cy);
   const double lim = 1048576.0;  // 2^20
   const bool ok = isfinite(p[2]) && isfinite(u) && isfinite(v) && p[2] >= cam.near && fabs(u) <= lim && fabs(v) <= lim;
   int2 o;
-  o.x = ok ? (int)rint(mr_mul(256.0, u)) : kMrFlag;
-  o.y = ok ? (int)rint(mr_mul(256.0, v)) : 0;
+  o.x = ok ? (int)rint(dmul(256.0, u)) : kMrFlag;
+  o.y = ok ? (int)rint(dmul(256.0, v)) : 0;
   xy[t] = o;
 }
 
@@ -321,9 +309,9 @@ __device__ __forceinline__ MrVec mr_load3(const float* __restrict__ p, int v) {
 __device__ __forceinline__ MrVec mr_blend(const float* __restrict__ attr, int a, int b, int c, double b0, double b1,
                                           double b2) {
   const MrVec p = mr_load3(attr, a), q = mr_load3(attr, b), r = mr_load3(attr, c);
-  return {mr_add(mr_add(mr_mul(b0, p.x), mr_mul(b1, q.x)), mr_mul(b2, r.x)),
-          mr_add(mr_add(mr_mul(b0, p.y), mr_mul(b1, q.y)), mr_mul(b2, r.y)),
-          mr_add(mr_add(mr_mul(b0, p.z), mr_mul(b1, q.z)), mr_mul(b2, r.z))};
+  return {dadd(dadd(dmul(b0, p.x), dmul(b1, q.x)), dmul(b2, r.x)),
+          dadd(dadd(dmul(b0, p.y), dmul(b1, q.y)), dmul(b2, r.y)),
+          dadd(dadd(dmul(b0, p.z), dmul(b1, q.z)), dmul(b2, r.z))};
 }
 
 __global__ __launch_bounds__(kMrWG) void mr_resolve(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -339,7 +327,7 @@ __global__ __launch_bounds__(kMrWG) void mr_resolve(const float* __restrict__ ve
   int a = 0, b = 0, c = 0;
   if (hit) {
     a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    hit = mr_valid(a, b, c, V);
+    hit = face_valid(a, b, c, V);
   }
   float rgb[3] = {(float)sh.background[0], (float)sh.background[1], (float)sh.background[2]};
   float depth = 0.f, zdepth = 0.f, nrm[3] = {0.f, 0.f, 0.f}, bary[3] = {0.f, 0.f, 0.f};
@@ -350,18 +338,18 @@ __global__ __launch_bounds__(kMrWG) void mr_resolve(const float* __restrict__ ve
     const MrPlane pl = mr_plane(pc, a, b, c);
     mr_tz(pl, xl, yl, tz);
     MrVec dw;
-    dw.x = mr_add(mr_add(mr_mul(cam.m[0], xl), mr_mul(cam.m[1], yl)), cam.m[2]);
-    dw.y = mr_add(mr_add(mr_mul(cam.m[3], xl), mr_mul(cam.m[4], yl)), cam.m[5]);
-    dw.z = mr_add(mr_add(mr_mul(cam.m[6], xl), mr_mul(cam.m[7], yl)), cam.m[8]);
+    dw.x = dadd(dadd(dmul(cam.m[0], xl), dmul(cam.m[1], yl)), cam.m[2]);
+    dw.y = dadd(dadd(dmul(cam.m[3], xl), dmul(cam.m[4], yl)), cam.m[5]);
+    dw.z = dadd(dadd(dmul(cam.m[6], xl), dmul(cam.m[7], yl)), cam.m[8]);
     const double len = __dsqrt_rn(mr_dot(dw, dw));
     zdepth = (float)tz;
-    depth = (float)mr_mul(tz, len);
-    const MrVec p = {mr_mul(tz, xl), mr_mul(tz, yl), tz};
+    depth = (float)dmul(tz, len);
+    const MrVec p = {dmul(tz, xl), dmul(tz, yl), tz};
     const MrVec w = mr_sub(p, pl.v0);
     const double nn = mr_dot(pl.n, pl.n);
-    const double b1 = mr_div(mr_dot(mr_cross(w, pl.e2), pl.n), nn);
-    const double b2 = mr_div(mr_dot(mr_cross(pl.e1, w), pl.n), nn);
-    const double b0 = mr_dif(mr_dif(1.0, b1), b2);
+    const double b1 = ddiv(mr_dot(mr_cross(w, pl.e2), pl.n), nn);
+    const double b2 = ddiv(mr_dot(mr_cross(pl.e1, w), pl.n), nn);
+    const double b0 = dsub(dsub(1.0, b1), b2);
     bary[0] = (float)b0, bary[1] = (float)b1, bary[2] = (float)b2;
     MrVec m;
     if (normals) {
@@ -372,15 +360,15 @@ __global__ __launch_bounds__(kMrWG) void mr_resolve(const float* __restrict__ ve
     }
     const double ml = __dsqrt_rn(mr_dot(m, m));
     MrVec nh = {0.0, 0.0, 0.0};
-    if (ml > 0.0 && isfinite(ml)) nh = {mr_div(m.x, ml), mr_div(m.y, ml), mr_div(m.z, ml)};
+    if (ml > 0.0 && isfinite(ml)) nh = {ddiv(m.x, ml), ddiv(m.y, ml), ddiv(m.z, ml)};
     nrm[0] = (float)nh.x, nrm[1] = (float)nh.y, nrm[2] = (float)nh.z;
-    const double cosv = fabs(mr_div(mr_dot(nh, dw), len));
-    const double shade = mr_add(sh.ambient, mr_mul(mr_dif(1.0, sh.ambient), cosv));
+    const double cosv = fabs(ddiv(mr_dot(nh, dw), len));
+    const double shade = dadd(sh.ambient, dmul(dsub(1.0, sh.ambient), cosv));
     MrVec base = {sh.base[0], sh.base[1], sh.base[2]};
     if (colors) base = mr_blend(colors, a, b, c, b0, b1, b2);
-    rgb[0] = (float)mr_mul(base.x, shade);
-    rgb[1] = (float)mr_mul(base.y, shade);
-    rgb[2] = (float)mr_mul(base.z, shade);
+    rgb[0] = (float)dmul(base.x, shade);
+    rgb[1] = (float)dmul(base.y, shade);
+    rgb[2] = (float)dmul(base.z, shade);
   }
   if (o.face_id) o.face_id[pix] = hit ? (int)f : -1;
   if (o.mask) o.mask[pix] = hit ? 1 : 0;
@@ -404,8 +392,6 @@ __global__ void mr_finish(const MrHeader* __restrict__ hdr, int64_t* __restrict_
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static size_t mr_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct MrPlan {
   int64_t npix;
   size_t o_xy, o_pc, o_keys, o_queue, total;
@@ -416,10 +402,10 @@ static bool mr_plan(int64_t V, int64_t F, int64_t H, int64_t W, MrPlan& p) {
   if (H > INT32_MAX / W) return false;  // H W < 2^31
   p.npix = H * W;
   size_t o = 256;  // MrHeader
-  p.o_xy = o; o += mr_a256((size_t)V * 8);
-  p.o_pc = o; o += mr_a256((size_t)V * 24);
-  p.o_keys = o; o += mr_a256((size_t)p.npix * 8);
-  p.o_queue = o; o += mr_a256((size_t)F * 4);
+  p.o_xy = o; o += a256((size_t)V * 8);
+  p.o_pc = o; o += a256((size_t)V * 24);
+  p.o_keys = o; o += a256((size_t)p.npix * 8);
+  p.o_queue = o; o += a256((size_t)F * 4);
   p.total = o;
   return true;
 }
@@ -472,34 +458,20 @@ int nr_mesh_render(const NrMeshRenderArgs* a, void* stream) {
   for (int k = 0; k < 3; ++k) sh.base[k] = a->base[k], sh.background[k] = a->background[k];
   const int64_t V = a->V, F = a->F;
   const int64_t nset = V > pl.npix ? V : pl.npix;
-  {
-    ProfScope prof("mr_setup", (double)V, st);
-    hipLaunchKernelGGL(mr_setup, dim3((unsigned)((nset + kMrWG - 1) / kMrWG)), dim3(kMrWG), 0, st, a->verts, V, cam, xy,
-                       pc, keys, pl.npix, hdr);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("mr_setup", (double)V, mr_setup, dim3((unsigned)((nset + kMrWG - 1) / kMrWG)), dim3(kMrWG), st, a->verts, V, cam,
+            xy, pc, keys, pl.npix, hdr);
   if (F > 0) {
     const int64_t nbf = (F + kMrWG - 1) / kMrWG;
-    {
-      ProfScope prof("mr_faces", (double)F, st);
-      hipLaunchKernelGGL(mr_faces, dim3((unsigned)nbf), dim3(kMrWG), 0, st, a->faces, F, V, cam, xy, pc,
-                         a->large_threshold, keys, queue, hdr);
-    }
-    NR_HIP_CHECK(hipGetLastError());
-    {
-      ProfScope prof("mr_large", (double)F, st);
-      hipLaunchKernelGGL(mr_large, dim3((unsigned)(F < kMrLargeGrid ? F : kMrLargeGrid)), dim3(kMrWG), 0, st, a->faces,
-                         F, V, cam, xy, pc, keys, queue, hdr);
-    }
-    NR_HIP_CHECK(hipGetLastError());
+    NR_LAUNCH("mr_faces", (double)F, mr_faces, dim3((unsigned)nbf), dim3(kMrWG), st, a->faces, F, V, cam, xy, pc,
+              a->large_threshold, keys, queue, hdr);
+    NR_LAUNCH("mr_large", (double)F, mr_large, dim3((unsigned)(F < kMrLargeGrid ? F : kMrLargeGrid)), dim3(kMrWG), st,
+              a->faces, F, V, cam, xy, pc, keys, queue, hdr);
   }
   if (a->rgb || a->depth || a->normal || a->mask || a->face_id || a->bary || a->zdepth) {
     MrOut o = {a->rgb, a->depth, a->normal, a->bary, a->zdepth, a->mask, a->face_id};
-    ProfScope prof("mr_resolve", (double)pl.npix, st);
-    hipLaunchKernelGGL(mr_resolve, dim3((unsigned)((pl.npix + kMrWG - 1) / kMrWG)), dim3(kMrWG), 0, st, a->verts,
-                       a->faces, a->normals, a->colors, F, V, cam, sh, pc, keys, o);
+    NR_LAUNCH("mr_resolve", (double)pl.npix, mr_resolve, dim3((unsigned)((pl.npix + kMrWG - 1) / kMrWG)), dim3(kMrWG), st,
+              a->verts, a->faces, a->normals, a->colors, F, V, cam, sh, pc, keys, o);
   }
-  NR_HIP_CHECK(hipGetLastError());
   if (a->counters) {
     hipLaunchKernelGGL(mr_finish, dim3(1), dim3(64), 0, st, hdr, a->counters);
     NR_HIP_CHECK(hipGetLastError());

@@ -4,8 +4,7 @@
 //
 // Every output is a pure function of the inputs (verts, faces, u): two runs are bit-identical.  All
 // arithmetic is float64 with each operation rounded on its own: `#pragma clang fp contract(off)` below the
-// includes and plain operators under it (HIP's __dmul_rn and its kin are plain * + - in a header parsed
-// before any pragma of this file and get fused; DESIGN.md, "Order independence").  The float64 division and
+// includes and plain operators under it (why not the __d*_rn intrinsics: nr_common.h).  The float64 division and
 // square root are correctly rounded, so tests/mesh_metrics_ref.py restates the sampler in numpy bit for bit.
 //
 // Definitions
@@ -52,7 +51,7 @@
 //     read, so a cdf that belongs to another mesh cannot cause an out-of-range read (face_id -1 then).
 //   info (device float64 [2]): {total, status}.
 // Workspace: 12 bytes per 2048 faces (W_q / B_q and a status word), each array rounded up to 256 bytes, at least 512.
-#include "nr_common.h"
+#include "nr_meshcommon.h"
 
 #pragma clang fp contract(off)  // no a * b + c -> fma anywhere in this file (header comment)
 
@@ -63,10 +62,6 @@ constexpr int kMsStrip = 8;                   // consecutive faces per thread
 constexpr int kMsBlock = kMsWG * kMsStrip;    // faces per workgroup
 
 enum { kMsBadIndex = 1, kMsNonFinite = 2 };
-
-__device__ __forceinline__ bool ms_valid(int a, int b, int c, int64_t V) {
-  return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
-}
 
 __device__ __forceinline__ double ms_area_of(const float* __restrict__ verts, int a, int b, int c) {
   const double x0 = verts[3 * (int64_t)a], y0 = verts[3 * (int64_t)a + 1], z0 = verts[3 * (int64_t)a + 2];
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(kMsWG) void ms_area(const float* __restrict__ verts
     double a = 0.0;
     if (f < F) {
       const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-      if (!ms_valid(ia, ib, ic, V)) {
+      if (!face_valid(ia, ib, ic, V)) {
         status |= kMsBadIndex;
       } else {
         a = ms_area_of(verts, ia, ib, ic);
@@ -211,7 +206,7 @@ __global__ __launch_bounds__(kMsWG) void ms_sample(const float* __restrict__ ver
   int ia = 0, ib = 0, ic = 0;
   if (face >= 0) {
     ia = faces[3 * face], ib = faces[3 * face + 1], ic = faces[3 * face + 2];
-    if (!ms_valid(ia, ib, ic, V)) face = -1;
+    if (!face_valid(ia, ib, ic, V)) face = -1;
   }
   if (face < 0) {
     points[3 * k] = 0.f, points[3 * k + 1] = 0.f, points[3 * k + 2] = 0.f;
@@ -235,8 +230,6 @@ __global__ __launch_bounds__(kMsWG) void ms_sample(const float* __restrict__ ver
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static size_t ms_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct MsPlan {
   int64_t nb;
   size_t o_sum, o_stat, total;
@@ -247,8 +240,8 @@ static bool ms_plan(int64_t F, MsPlan& p) {
   p.nb = (F + kMsBlock - 1) / kMsBlock;
   const size_t slots = (size_t)(p.nb > 0 ? p.nb : 1);
   size_t o = 0;
-  p.o_sum = o; o += ms_a256(slots * 8);
-  p.o_stat = o; o += ms_a256(slots * 4);
+  p.o_sum = o; o += a256(slots * 8);
+  p.o_stat = o; o += a256(slots * 4);
   p.total = o;
   return true;
 }
@@ -276,21 +269,11 @@ int nr_mesh_face_cdf(const float* verts, int64_t V, const int32_t* faces, int64_
   char* ws = (char*)workspace;
   double* wsum = (double*)(ws + pl.o_sum);
   unsigned* wstat = (unsigned*)(ws + pl.o_stat);
-  if (F > 0) {
-    ProfScope prof("mesh_area", (double)F, st);
-    hipLaunchKernelGGL(ms_area, dim3((unsigned)pl.nb), dim3(kMsWG), 0, st, verts, V, faces, F, cdf, wsum, wstat);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  {
-    ProfScope prof("mesh_area_scan", (double)pl.nb, st);
-    hipLaunchKernelGGL(ms_scan, dim3(1), dim3(kMsWG), 0, st, wsum, wstat, pl.nb, info);
-  }
-  NR_HIP_CHECK(hipGetLastError());
-  if (pl.nb > 1) {  // a single workgroup has base 0: 0 + x == x
-    ProfScope prof("mesh_area_fix", (double)F, st);
-    hipLaunchKernelGGL(ms_fix, dim3((unsigned)((F + kMsWG - 1) / kMsWG)), dim3(kMsWG), 0, st, cdf, F, wsum);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  if (F > 0)
+    NR_LAUNCH("mesh_area", (double)F, ms_area, dim3((unsigned)pl.nb), dim3(kMsWG), st, verts, V, faces, F, cdf, wsum, wstat);
+  NR_LAUNCH("mesh_area_scan", (double)pl.nb, ms_scan, dim3(1), dim3(kMsWG), st, wsum, wstat, pl.nb, info);
+  if (pl.nb > 1)  // a single workgroup has base 0: 0 + x == x
+    NR_LAUNCH("mesh_area_fix", (double)F, ms_fix, dim3((unsigned)((F + kMsWG - 1) / kMsWG)), dim3(kMsWG), st, cdf, F, wsum);
   return NR_OK;
 }
 
@@ -304,12 +287,8 @@ int nr_mesh_sample(const float* verts, int64_t V, const int32_t* faces, int64_t 
   NR_REQUIRE((points && face_id) || n == 0, NR_ERR_ARG, "nr_mesh_sample: null output");
   if (n == 0) return NR_OK;
   hipStream_t st = (hipStream_t)stream;
-  {
-    ProfScope prof("mesh_sample", (double)n, st);
-    hipLaunchKernelGGL(ms_sample, dim3((unsigned)((n + kMsWG - 1) / kMsWG)), dim3(kMsWG), 0, st, verts, V, faces, F,
-                       cdf, u, n, points, face_id);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("mesh_sample", (double)n, ms_sample, dim3((unsigned)((n + kMsWG - 1) / kMsWG)), dim3(kMsWG), st, verts, V, faces,
+            F, cdf, u, n, points, face_id);
   return NR_OK;
 }
 

@@ -5,8 +5,8 @@
 //
 // THE RULE (tests/mesh_metrics_ref.py restates it as a dense brute force; the results are the same bits)
 //   points fp32 [N, 3], queries fp32 [M, 3].  Per pair, float64, every operation rounded on its own
-//   (`#pragma clang fp contract(off)` below the includes, plain operators under it; DESIGN.md "Order
-//   independence" on why not __dmul_rn):
+//   (`#pragma clang fp contract(off)` below the includes, plain operators under it; nr_common.h on why
+//   not __dmul_rn):
 //       dx = (double) q.x - (double) p.x,  dy, dz alike;   d2 = ((dx dx) + (dy dy)) + (dz dz)
 //   The neighbour of q is the point with the smallest (d2, index), compared lexicographically: a tie in d2
 //   goes to the smaller index.  With max_dist (>= 0, +inf = none) the result is kept iff d2 <= max_dist max_dist
@@ -66,7 +66,7 @@
 // Workspace (nr_nn_workspace_bytes(N, M)), C = CAP(N):  256 header bytes + 2 x 4 (C + 1) (cell tables of the
 // points and of the queries) + 4 ceil((C + 1) / 1024) (scan sums) + 16 N (records) + 4 M (query order), each
 // array rounded up to 256 bytes.  nr_nn_build needs the part up to the records: nr_nn_workspace_bytes(N, 0).
-#include "nr_common.h"
+#include "nr_meshcommon.h"
 
 #pragma clang fp contract(off)  // no a * b + c -> fma anywhere in this file (header comment)
 
@@ -328,30 +328,12 @@ __global__ __launch_bounds__(kNnWG) void nn_scan_sums(const int* __restrict__ ta
   if (threadIdx.x == 0) sums[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
-// one workgroup; sums[b] = items before workgroup b (thread t owns a contiguous strip, as mo_scan)
+// one workgroup; sums[b] = items before workgroup b
 __global__ __launch_bounds__(kNnScanWG) void nn_scan_top(int* __restrict__ sums, const NnHeader* __restrict__ hdr) {
   __shared__ int s[kNnScanWG];
   const int64_t n = (int64_t)hdr->cells + 1;
-  const int64_t nb = (n + kNnScanItems - 1) / kNnScanItems;
-  const int tid = threadIdx.x;
-  const int64_t L = (nb + kNnScanWG - 1) / kNnScanWG;
-  const int64_t lo = tid * L < nb ? tid * L : nb, hi = lo + L < nb ? lo + L : nb;
-  int a = 0;
-  for (int64_t q = lo; q < hi; ++q) a += sums[q];
-  s[tid] = a;
-  __syncthreads();
-  for (int off = 1; off < kNnScanWG; off <<= 1) {
-    const int x = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += x;
-    __syncthreads();
-  }
-  int e = s[tid] - a;
-  for (int64_t q = lo; q < hi; ++q) {
-    const int c = sums[q];
-    sums[q] = e;
-    e += c;
-  }
+  strip_scan<kNnScanWG>((n + kNnScanItems - 1) / kNnScanItems, s, [&](int64_t q) { return sums[q]; },
+                        [&](int64_t q, int e) { sums[q] = e; });
 }
 
 __global__ __launch_bounds__(kNnWG) void nn_scan_fix(int* __restrict__ table, const NnHeader* __restrict__ hdr,
@@ -500,8 +482,6 @@ __global__ void nn_qfinish(const NnHeader* __restrict__ hdr, int64_t* __restrict
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static size_t nn_a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct NnPlan {
   int64_t cap, nsb;  // cell cap, scan workgroups
   size_t o_ptable, o_qtable, o_sums, o_recs, o_order, build_total, total;
@@ -513,12 +493,12 @@ static bool nn_plan_host(int64_t N, int64_t M, NnPlan& p) {
   if (p.cap < 1) p.cap = 1;
   p.nsb = (p.cap + 1 + kNnScanItems - 1) / kNnScanItems;
   size_t o = 256;  // NnHeader
-  p.o_ptable = o; o += nn_a256((size_t)(p.cap + 1) * 4);
-  p.o_qtable = o; o += nn_a256((size_t)(p.cap + 1) * 4);
-  p.o_sums = o; o += nn_a256((size_t)p.nsb * 4);
-  p.o_recs = o; o += nn_a256((size_t)N * 16);
+  p.o_ptable = o; o += a256((size_t)(p.cap + 1) * 4);
+  p.o_qtable = o; o += a256((size_t)(p.cap + 1) * 4);
+  p.o_sums = o; o += a256((size_t)p.nsb * 4);
+  p.o_recs = o; o += a256((size_t)N * 16);
   p.build_total = o;
-  p.o_order = o; o += nn_a256((size_t)M * 4);
+  p.o_order = o; o += a256((size_t)M * 4);
   p.total = o;
   return true;
 }
@@ -559,10 +539,7 @@ int nr_nn_bounds(const float* points, int64_t N, double* bounds, void* workspace
   hipStream_t st = (hipStream_t)stream;
   NnHeader* hdr = (NnHeader*)workspace;
   hipLaunchKernelGGL(nn_init, dim3(1), dim3(64), 0, st, hdr);
-  if (N > 0) {
-    ProfScope prof("nn_bounds", (double)N, st);
-    hipLaunchKernelGGL(nn_bounds, dim3(nn_bounds_blocks(N)), dim3(kNnWG), 0, st, points, N, hdr);
-  }
+  if (N > 0) NR_LAUNCH("nn_bounds", (double)N, nn_bounds, dim3(nn_bounds_blocks(N)), dim3(kNnWG), st, points, N, hdr);
   hipLaunchKernelGGL(nn_box, dim3(1), dim3(64), 0, st, hdr, bounds);
   NR_HIP_CHECK(hipGetLastError());
   return NR_OK;
@@ -582,24 +559,17 @@ int nr_nn_build(const float* points, int64_t N, double h, void* workspace, size_
   float4* recs = (float4*)(ws + pl.o_recs);
   hipLaunchKernelGGL(nn_init, dim3(1), dim3(64), 0, st, hdr);
   NR_HIP_CHECK(hipMemsetAsync(ptable, 0, (size_t)(pl.cap + 1) * 4, st));
-  if (N > 0) {
-    ProfScope prof("nn_bounds", (double)N, st);
-    hipLaunchKernelGGL(nn_bounds, dim3(nn_bounds_blocks(N)), dim3(kNnWG), 0, st, points, N, hdr);
-  }
+  if (N > 0) NR_LAUNCH("nn_bounds", (double)N, nn_bounds, dim3(nn_bounds_blocks(N)), dim3(kNnWG), st, points, N, hdr);
   hipLaunchKernelGGL(nn_box, dim3(1), dim3(64), 0, st, hdr, (double*)nullptr);
   hipLaunchKernelGGL(nn_plan, dim3(1), dim3(64), 0, st, hdr, h, pl.cap, N);
   NR_HIP_CHECK(hipGetLastError());
-  if (N > 0) {
-    ProfScope prof("nn_hist", (double)N, st);
-    hipLaunchKernelGGL(nn_hist, dim3(nn_blocks(N)), dim3(kNnWG), 0, st, points, N, hdr, ptable, 0, (int*)nullptr,
-                       (double*)nullptr);
-  }
+  if (N > 0)
+    NR_LAUNCH("nn_hist", (double)N, nn_hist, dim3(nn_blocks(N)), dim3(kNnWG), st, points, N, hdr, ptable, 0, (int*)nullptr,
+              (double*)nullptr);
   nn_scan("nn_scan", ptable, hdr, sums, pl, st);
-  if (N > 0) {
-    ProfScope prof("nn_scatter", (double)N, st);
-    hipLaunchKernelGGL(nn_scatter, dim3(nn_blocks(N)), dim3(kNnWG), 0, st, points, N, hdr, ptable, recs,
-                       (int*)nullptr, N);
-  }
+  if (N > 0)
+    NR_LAUNCH("nn_scatter", (double)N, nn_scatter, dim3(nn_blocks(N)), dim3(kNnWG), st, points, N, hdr, ptable, recs,
+              (int*)nullptr, N);
   NR_HIP_CHECK(hipGetLastError());
   return NR_OK;
 }
@@ -624,21 +594,12 @@ int nr_nn_query(int64_t N, const float* queries, int64_t M, double max_dist, int
   NR_HIP_CHECK(hipGetLastError());
   if (M > 0) {
     NR_HIP_CHECK(hipMemsetAsync(qtable, 0, (size_t)(pl.cap + 1) * 4, st));
-    {
-      ProfScope prof("nn_qhist", (double)M, st);
-      hipLaunchKernelGGL(nn_hist, dim3(nn_blocks(M)), dim3(kNnWG), 0, st, queries, M, hdr, qtable, 1, index, d2);
-    }
+    NR_LAUNCH("nn_qhist", (double)M, nn_hist, dim3(nn_blocks(M)), dim3(kNnWG), st, queries, M, hdr, qtable, 1, index, d2);
     nn_scan("nn_qscan", qtable, hdr, sums, pl, st);
-    {
-      ProfScope prof("nn_qscatter", (double)M, st);
-      hipLaunchKernelGGL(nn_scatter, dim3(nn_blocks(M)), dim3(kNnWG), 0, st, queries, M, hdr, qtable,
-                         (float4*)nullptr, order, M);
-    }
-    {
-      ProfScope prof("nn_query", (double)M, st);
-      hipLaunchKernelGGL(nn_query, dim3(nn_blocks(M)), dim3(kNnWG), 0, st, queries, M, N, hdr, ptable, qtable, recs,
-                         order, max_dist, index, d2);
-    }
+    NR_LAUNCH("nn_qscatter", (double)M, nn_scatter, dim3(nn_blocks(M)), dim3(kNnWG), st, queries, M, hdr, qtable,
+              (float4*)nullptr, order, M);
+    NR_LAUNCH("nn_query", (double)M, nn_query, dim3(nn_blocks(M)), dim3(kNnWG), st, queries, M, N, hdr, ptable, qtable, recs,
+              order, max_dist, index, d2);
   }
   hipLaunchKernelGGL(nn_qfinish, dim3(1), dim3(64), 0, st, hdr, status);
   NR_HIP_CHECK(hipGetLastError());

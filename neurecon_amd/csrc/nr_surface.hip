@@ -8,7 +8,7 @@
 //     rays;
 //   * the mesh-extraction grid (utils/mesh_util.py:82-112 `extract_mesh`): voxel coordinates
 //     generated on the device with the reference's own float64 formula, then the forward SDF.
-#include "nr_common.h"
+#include "nr_meshcommon.h"
 #include "nr_mlp.h"
 #include "nr_unisurf.h"
 
@@ -120,23 +120,21 @@ __global__ void surface_finish(float* __restrict__ rgb, const float* __restrict_
 
 // extract_mesh voxel coordinates (mesh_util.py:87-100), float64 exactly as numpy evaluates them —
 // including the reference's true divisions: x = ((i/N)/N) % N, y = (i/N) % N, z = i % N — then
-// coordinate = index * (s/(N-1)) + origin (no FMA), cast to float32 (`.float()`, :104).
+// coordinate = index * (s/(N-1)) + origin (dmul then dadd, never one FMA), cast to float32 (`.float()`, :104).
 __global__ void grid_points_kernel(int64_t N, double step, double origin, int64_t i0, int64_t n,
                                    float* __restrict__ pts) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const int64_t i = i0 + t;
   const double Nd = (double)N;
-  const double qi = __ddiv_rn((double)i, Nd);
+  const double qi = ddiv((double)i, Nd);
   const double z = (double)(i % N);
   const double y = fmod(qi, Nd);
-  const double x = fmod(__ddiv_rn(qi, Nd), Nd);
-  pts[t * 3 + 0] = (float)__dadd_rn(__dmul_rn(x, step), origin);
-  pts[t * 3 + 1] = (float)__dadd_rn(__dmul_rn(y, step), origin);
-  pts[t * 3 + 2] = (float)__dadd_rn(__dmul_rn(z, step), origin);
+  const double x = fmod(ddiv(qi, Nd), Nd);
+  pts[t * 3 + 0] = (float)dadd(dmul(x, step), origin);
+  pts[t * 3 + 1] = (float)dadd(dmul(y, step), origin);
+  pts[t * 3 + 2] = (float)dadd(dmul(z, step), origin);
 }
-
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct TracePlan {
   size_t o_idx0, o_idx1, o_pts, o_sv, o_cnt, total;
@@ -215,12 +213,8 @@ int nr_sphere_trace(const NrSdfDesc* d, const void* packed, const float* rays_o,
   float* sv = (float*)(ws + pl.o_sv);
   int* cnt = (int*)(ws + pl.o_cnt);  // cnt[0], cnt[1]: active counts of the two lists
   const SdfLayout SL = sdf_layout(*d);
-  {
-    ProfScope prof("trace_init", (double)n_rays, st);
-    hipLaunchKernelGGL(trace_init, grid1(n_rays), dim3(256), 0, st, rays_o, rays_d, n_rays, near, near_rays, d_pred,
-                       mask, idx[0], qp);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("trace_init", (double)n_rays, trace_init, grid1(n_rays), dim3(256), st, rays_o, rays_d, n_rays, near, near_rays,
+            d_pred, mask, idx[0], qp);
   NR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)cnt, (int)n_rays, 1, st));
   for (int it = 0; it < n_iters; ++it) {
     const int cur = it & 1, nxt = cur ^ 1;
@@ -229,12 +223,8 @@ int nr_sphere_trace(const NrSdfDesc* d, const void* packed, const float* rays_o,
       return rc;
     const int append = it + 1 < n_iters;
     NR_HIP_CHECK(hipMemsetAsync(cnt + nxt, 0, sizeof(int), st));
-    {
-      ProfScope prof("trace_step", (double)n_rays, st);
-      hipLaunchKernelGGL(trace_step, grid1(n_rays), dim3(256), 0, st, rays_o, rays_d, cnt + cur, idx[cur], sv, far,
-                         far_rays, d_pred, mask, cnt + nxt, idx[nxt], qp, append);
-    }
-    NR_HIP_CHECK(hipGetLastError());
+    NR_LAUNCH("trace_step", (double)n_rays, trace_step, grid1(n_rays), dim3(256), st, rays_o, rays_d, cnt + cur, idx[cur],
+              sv, far, far_rays, d_pred, mask, cnt + nxt, idx[nxt], qp, append);
   }
   hipLaunchKernelGGL(trace_final, grid1(n_rays), dim3(256), 0, st, rays_o, rays_d, n_rays, d_pred, pts);
   NR_HIP_CHECK(hipGetLastError());
@@ -291,12 +281,8 @@ int nr_root_find(const NrSdfDesc* d, const void* packed, const float* rays_o, co
     c.pts_m = F(pl.o_ptsm); c.sm = F(pl.o_sm); c.sec = F(pl.o_sec); c.pts_s = F(pl.o_ptss); c.ss = F(pl.o_ss);
     c.t_march = t_march;
     const dim3 blk(64), grd((R + 63) / 64);
-    {
-      ProfScope prof("root_prologue", (double)R, st);
-      hipLaunchKernelGGL(rf_prologue, grd, blk, 0, st, c, rays_o + r0 * 3, rays_d + r0 * 3, near, far,
-                         near_rays ? near_rays + r0 : nullptr, far_rays ? far_rays + r0 : nullptr);
-    }
-    NR_HIP_CHECK(hipGetLastError());
+    NR_LAUNCH("root_prologue", (double)R, rf_prologue, grd, blk, st, c, rays_o + r0 * 3, rays_d + r0 * 3, near, far,
+              near_rays ? near_rays + r0 : nullptr, far_rays ? far_rays + r0 : nullptr);
     // the march in chunks of kMarchK steps over the rays still without a sign change (uni_root reads a
     // ray's march only up to its first crossing); full_march: every step of every ray in one launch
     if ((rc = run_march(SL, packed, d->multires, c, full_march != 0, (int*)(ws + pl.o_act0), (int*)(ws + pl.o_act1),
@@ -329,11 +315,7 @@ int nr_sdf_grid(const NrSdfDesc* d, const void* packed, double volume_size, int6
   hipStream_t st = (hipStream_t)stream;
   float* pts = (float*)workspace;
   const double step = volume_size / (double)(N - 1), origin = -volume_size / 2.0;
-  {
-    ProfScope prof("grid_points", (double)n, st);
-    hipLaunchKernelGGL(grid_points_kernel, grid1(n), dim3(256), 0, st, N, step, origin, i0, n, pts);
-  }
-  NR_HIP_CHECK(hipGetLastError());
+  NR_LAUNCH("grid_points", (double)n, grid_points_kernel, grid1(n), dim3(256), st, N, step, origin, i0, n, pts);
   return launch_sdf(sdf_layout(*d), packed, pts, n, sdf, nullptr, nullptr, d->multires, nullptr, 0, st);
 }
 

@@ -3,8 +3,9 @@ and of extract_mesh's native path end to end.
 
 The numpy reference below computes the crossing-edge list in the order nr_mcubes.hip defines (owning
 point's flat C index, then axis) and the positions by the float64 formula rounded to fp32 once.
-Position bar: one fp32 ulp of the largest |coordinate| in the mesh -- the only licence the kernel has is
-fused multiply-add contraction of the float64 expression before the single rounding.  Faces are checked
+The kernel rounds every float64 operation on its own, as numpy does, and its division is IEEE, so
+check_mesh compares positions by equality; the few direct comparisons outside it keep the older bar of
+one fp32 ulp of the largest |coordinate| in the mesh.  Faces are checked
 by their properties (one cell per face, cell order, closed and consistently oriented surface, Euler
 characteristic, signed volume) and, as the orders are fully defined, against the list the case table
 (nr_mc_table) gives in numpy."""
@@ -137,13 +138,14 @@ def run_mc(vol, level=0.0, **kw):
 
 
 def check_mesh(vol, level=0.0, **kw):
-    """verts vs the reference list (count exact, order, one-ulp bar), faces vs the table-derived list"""
+    """verts vs the reference list (count exact, order, positions equal), faces vs the table-derived list"""
     key, ref = ref_vertices(vol, level, **kw)
     verts, faces = run_mc(vol, level, **kw)
     assert verts.shape == ref.shape, (verts.shape, ref.shape)
     err = np.abs(verts.astype(np.float64) - ref.astype(np.float64)).max()
-    print(f'{np.asarray(vol).shape} level {level}: V={len(verts)} F={len(faces)} max |dpos| {err:.3e} (bar {ulp_bar(ref):.3e})')
-    assert err <= ulp_bar(ref)
+    print(f'{np.asarray(vol).shape} level {level}: V={len(verts)} F={len(faces)} max |dpos| {err:.3e} '
+          f'({int((verts != ref).sum())} coordinates differ)')
+    assert np.array_equal(verts, ref)
     want, _ = ref_faces(vol, level, key)
     assert faces.shape == want.shape and np.array_equal(faces, want)
     return key, ref, verts, faces
@@ -218,6 +220,28 @@ def test_more_workgroups_than_scan_threads():
     vol = np.random.default_rng(1).standard_normal(shape).astype(np.float32)
     vol += 4 * _sphere(shape, (0.1, -0.2, 0.05), 0.7)                          # fewer crossings than pure noise
     check_mesh(vol, 0.25)
+
+
+@pytest.mark.parametrize('axis', [0, 1, 2])
+def test_product_and_sum_are_rounded_separately(axis):
+    """vol = index along `axis` - 2.3, rounded to fp32: every vertex sits on an edge from 2 to 3 of that axis, at
+    t = 0.30000001192092896, idx = 2.300000011920929 in float64 from the fp32 ends.  origin[axis] =
+    -(idx * spacing[axis]) cancels the rounded product exactly, so the position is 0.0 on that axis for all
+    25 vertices; one fused multiply-add keeps the product's rounding error instead (1.7e-18, -3.3e-18,
+    -1.3e-17 for spacings 0.1, 0.3, 0.7)."""
+    shape = [1, 1, 1]
+    shape[axis] = 5
+    line = (np.arange(5) - 2.3).astype(np.float32)
+    vol = np.broadcast_to(line.reshape(shape), (5, 5, 5))
+    v0, v1 = np.float64(line[2]), np.float64(line[3])
+    idx = np.float64(2.0) + (np.float64(0.0) - v0) / (v1 - v0)
+    assert idx == 2.300000011920929
+    spacing = np.array([0.1, 0.3, 0.7])
+    origin = np.zeros(3)
+    origin[axis] = -(idx * spacing[axis])
+    _, ref, verts, _ = check_mesh(vol, 0.0, spacing=spacing, origin=origin)
+    assert len(ref) == 25 and (ref[:, axis] == 0.0).all()
+    assert np.array_equal(verts, ref)
 
 
 def test_watertight_and_oriented_on_every_case():

@@ -292,6 +292,20 @@ def test_vertex_mask_path():
         filter_mesh(verts, faces, vertex_mask=torch.ones(V - 1, dtype=torch.bool, device='cuda'))
 
 
+def test_filter_with_more_workgroups_than_scan_threads():
+    """1172 workgroups of 256 vertices and 2344 of 256 faces: each scan workgroup's 1024 threads own strips of
+    2 and 3 workgroups, the last strips partly or wholly empty (every other case here has one workgroup per
+    scan thread at most)"""
+    from neurecon_amd.mesh_util import filter_mesh
+    V, F = 300001, 600001
+    assert ((V + 255) // 256, (F + 255) // 256) == (1172, 2344)
+    faces = torch.from_numpy(soup(V, F, seed=3)).cuda()
+    verts = torch.from_numpy(np.random.default_rng(4).standard_normal((V, 3)).astype(np.float32)).cuda()
+    mask = np.random.default_rng(5).random(V) < 0.6
+    _, f2 = check_filtered(verts, faces, mask, filter_mesh(verts, faces, vertex_mask=torch.from_numpy(mask).cuda()))
+    assert 0 < len(f2) < F
+
+
 # ------------------------------------------------------------------------------------------------
 # attributes
 # ------------------------------------------------------------------------------------------------

@@ -214,6 +214,46 @@ def test_sdf_grid_range_matches_full_grid():
         sdf_grid_range(m.implicit_surface, 1.5, N, N ** 3 - 3, 4)
 
 
+@pytest.mark.parametrize('N, s', [(7, 2.0), (11, 2.0), (13, 2.5)])
+def test_sdf_grid_coordinates_are_numpys_bit_for_bit(N, s):
+    """The voxel coordinates nr_sdf_grid leaves in its workspace (exactly the [n, 3] fp32 buffer) equal the
+    float64 restatement of grid_points_kernel's comment on every bit: x = ((i/N)/N) % N, y = (i/N) % N,
+    z = i % N, coord = index * (s/(N-1)) + (-s/2), each operation rounded on its own, cast to fp32.
+    Where an index is exactly the centre k = (N-1)/2 the product rounds to s/2 and the sum is 0.0; one
+    fused multiply-add leaves -+5.55e-17 there instead, which is how this test tells the two apart.
+    With the true divisions the centre voxel's own x and y indices are fractional (k + k/N + ...), so of
+    its three coordinates only z is 0.0; the zero is asserted at every entry whose index is exactly k,
+    which occurs on each of the three axes."""
+    import ctypes
+    from neurecon_amd import _lib
+    lib = _lib.lib()
+    m = neus_model(wg.neus_state(seed=1), precision='fp32')
+    dev = torch.device('cuda')
+    desc, packed = m.implicit_surface.nr_packed(dev)
+    n = N ** 3
+    ws_bytes = lib.nr_sdf_grid_workspace_bytes(n)
+    assert ws_bytes >= 12 * n
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+    sdf = torch.empty(n, device=dev)
+    _lib.check(lib.nr_sdf_grid(ctypes.byref(desc), _lib.ptr(packed), ctypes.c_double(s), N, 0, n, _lib.ptr(sdf),
+                               _lib.ptr(ws), ws_bytes, _lib.stream_of(dev)))
+    torch.cuda.synchronize()
+    got = ws[:12 * n].cpu().numpy().view(np.float32).reshape(n, 3)
+    i = np.arange(n, dtype=np.int64)
+    idx = np.stack([((i / N) / N) % N, (i / N) % N, (i % N).astype(np.float64)], -1)
+    ref64 = idx * np.float64(s / (N - 1)) + np.float64(-s / 2.0)
+    ref = ref64.astype(np.float32)
+    bad = np.argwhere(got.view(np.uint32) != ref.view(np.uint32))
+    print(f'grid {N}^3, s {s}: {len(bad)} of {3 * n} coordinates differ from the restatement', bad[:5].tolist())
+    k = (N - 1) // 2
+    at_k = idx == float(k)
+    assert at_k[:, 0].any() and at_k[:, 1].any() and at_k[:, 2].any()
+    assert (ref64[at_k] == 0.0).all()
+    assert at_k[(n - 1) // 2, 2] and got[(n - 1) // 2, 2] == 0.0       # the centre voxel
+    assert (got[at_k] == 0.0).all()
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
 @pytest.mark.parametrize('precision', ['f16x3', 'fp32'])
 def test_root_finding_chunked_march_bit_identical(precision):
     """nr_root_find's march runs in chunks of 32 steps over the rays still without a sign change
