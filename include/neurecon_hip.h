@@ -598,6 +598,60 @@ size_t nr_mesh_render_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W
 int nr_mesh_render(const NrMeshRenderArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh culling on the device (nr_meshcull.hip): what the published DTU numbers apply to a mesh before the
+ * Chamfer distance is taken.  Each vertex is projected into every training camera; a vertex that lands
+ * outside a dilated object mask in a view that sees it is removed, and optionally one that no camera sees
+ * in front of the mesh's own depth.  Two steps, both pure functions of their inputs (integers and bytes:
+ * two runs are bit-identical, tests/mesh_cull_ref.py restates them in numpy and the device is compared by
+ * equality).  The rules in full: the header comment of nr_meshcull.hip.
+ *
+ * nr_mask_dilate   in, out uint8 [B, H, W], not aliased.  out[b, j, i] = 1 iff some in-image pixel (j', i')
+ *   with |j' - j| <= radius and |i' - i| <= radius has in[b, j', i'] != 0, else 0: a square structuring
+ *   element of side 2 radius + 1, pixels outside the image count as 0 (cv2.dilate with np.ones((k, k)),
+ *   scipy.ndimage.binary_dilation with a structure of ones).  radius = 0 copies in != 0; a radius beyond the
+ *   image is legal.  0 <= radius < 2^15, H, W > 0, H W < 2^31, B >= 0, B H W < 2^32.  Separable, and the cost
+ *   per pixel does not depend on the radius.
+ *   nr_mask_dilate_workspace_bytes  one byte per pixel, rounded up to 256 bytes (0 on bad counts).
+ *
+ * nr_mesh_view_test   the vertex stage of nr_mesh_render against a batch of cameras.
+ *   verts fp32 [V, 3]; cams float64 [n_views, 18] on the device, per row: rows 0..2 of world -> camera (12
+ *   values, row-major, as nr_mesh_render takes them), fx, fy, cx, cy, skew, near.  masks uint8 [n_views, H, W]
+ *   or NULL; zdepth fp32 [n_views, H, W] and face_id int32 [n_views, H, W] (nr_mesh_render's outputs of the
+ *   same cameras) both or neither; depth_tol finite, >= 0.
+ *   Per vertex and view, with p_c, u, v computed operation for operation as nr_mesh_render computes them:
+ *     in_image (bit 1)  p_c.z, u, v finite, p_c.z >= near, 0 <= u <= W - 1 and 0 <= v <= H - 1
+ *     in_mask  (bit 2)  in_image, masks given, masks[view, (int) rint(v), (int) rint(u)] != 0 (nearest pixel,
+ *                       round half to even)
+ *     visible  (bit 4)  in_image, zdepth given, p_c.z <= zmax + depth_tol; zmax = the maximum over the four
+ *                       samples (floor(v) | min(floor(v) + 1, H - 1), floor(u) | min(floor(u) + 1, W - 1)), a
+ *                       sample being +inf where face_id < 0 (a miss), else (double) zdepth.  Conservative at
+ *                       a silhouette: a footprint that touches a miss says visible.
+ *   flags uint8 [n_views, V] or NULL: the OR of the bits; counts int32 [V, 3] or NULL: (n_in_image, n_in_mask,
+ *   n_visible) over the views of the call, overwritten (accumulate = 0) or added to (accumulate = 1).
+ *   0 <= V <= INT32_MAX, 0 <= n_views <= INT32_MAX, H, W > 0, H W < 2^31; V == 0 and n_views == 0 are valid.
+ *   No polygon or near-plane clipping: the limit is nr_mesh_render's.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* verts;
+  int64_t V;
+  int64_t n_views;
+  const double* cams;     /* [n_views, 18] */
+  int64_t H, W;
+  const uint8_t* masks;   /* [n_views, H, W] or NULL */
+  const float* zdepth;    /* [n_views, H, W] or NULL */
+  const int32_t* face_id; /* [n_views, H, W], given exactly when zdepth is */
+  double depth_tol;
+  uint8_t* flags;         /* [n_views, V] or NULL */
+  int32_t* counts;        /* [V, 3] or NULL */
+  int accumulate;
+} NrMeshViewArgs;
+
+size_t nr_mask_dilate_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int nr_mask_dilate(const uint8_t* in, uint8_t* out, int64_t B, int64_t H, int64_t W, int64_t radius, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int nr_mesh_view_test(const NrMeshViewArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh evaluation on the device: points on the surface (nr_meshsample.hip) and the exact nearest
  * neighbour between two point clouds (nr_nn.hip), the two halves of the protocol NeuS, VolSDF and
  * UNISURF are published against (accuracy / completeness / Chamfer distance of the extracted mesh to a

@@ -157,6 +157,14 @@ class NrMeshRenderArgs(ctypes.Structure):
     ]
 
 
+class NrMeshViewArgs(ctypes.Structure):
+    _fields_ = [
+        ('verts', _c_p), ('V', _c_i64), ('n_views', _c_i64), ('cams', _c_p), ('H', _c_i64), ('W', _c_i64),
+        ('masks', _c_p), ('zdepth', _c_p), ('face_id', _c_p), ('depth_tol', _c_d), ('flags', _c_p), ('counts', _c_p),
+        ('accumulate', _c_i),
+    ]
+
+
 class NrKernelStat(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 32), ('launches', _c_i64), ('ms', ctypes.c_double),
                 ('units', ctypes.c_double)]
@@ -230,6 +238,10 @@ _SIGS = {
     # mesh rendering (nr_meshrender.hip)
     'nr_mesh_render_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     'nr_mesh_render': (_c_i, [ctypes.POINTER(NrMeshRenderArgs), _c_p]),
+    # mesh culling by camera masks and visibility (nr_meshcull.hip)
+    'nr_mask_dilate_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    'nr_mask_dilate': (_c_i, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_sz, _c_p]),
+    'nr_mesh_view_test': (_c_i, [ctypes.POINTER(NrMeshViewArgs), _c_p]),
     # mesh evaluation: surface samples (nr_meshsample.hip) and exact nearest neighbour (nr_nn.hip)
     'nr_mesh_sample_workspace_bytes': (_c_sz, [_c_i64]),
     'nr_mesh_face_cdf': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_sz, _c_p]),

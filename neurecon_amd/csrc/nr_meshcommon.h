@@ -1,5 +1,5 @@
 // neurecon_amd — the building blocks the mesh kernels share (nr_mcubes, nr_meshops, nr_meshsample, nr_nn,
-// nr_meshrender) and nr_surface's workspace plans: the workspace round-up, the face-index check, the
+// nr_meshrender, nr_meshcull) and nr_surface's workspace plans: the workspace round-up, the face-index check, the
 // workgroup prefix over wave totals and the one-workgroup scan of per-workgroup sums.  Exact fp32 / fp64
 // arithmetic (f* / d*) and the launch helper are in nr_common.h.
 #pragma once

@@ -24,7 +24,9 @@ the header comments of the two .hip files and restated in numpy in tests/mesh_me
 
 Out of scope: DTU's greedy radius thinning of the sampled cloud (the stratified sampler gives an even cloud
 instead), reading DTU's `.mat` ObsMask / plane files (pass the mask you derived from them as `gt_mask`),
-point-to-triangle distance (distances are between points: sample densely), sharding across ranks.
+point-to-triangle distance (distances are between points: sample densely), sharding across ranks.  Culling
+the mesh by the cameras' masks and visibility before it is scored, as the published DTU figures do, is
+`neurecon_amd.mesh_cull`.
 """
 import argparse
 import ctypes

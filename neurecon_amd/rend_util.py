@@ -39,6 +39,34 @@ def get_rays(c2w, intrinsics, H, W, N_rays=-1, device_rng=False):
     return ro.reshape(*prefix, N, 3), rd.reshape(*prefix, N, 3), select_inds
 
 
+def load_K_Rt_from_P(P):
+    """rend_util.py:8-25 without OpenCV: split a projection matrix P [3, 4] = s K [R | -R c] (any scale s, either
+    sign) into -> (intrinsics [4, 4] float64 holding K with K[2, 2] = 1 and a positive diagonal, pose [4, 4]
+    float32 holding R.T and the camera centre c: camera -> world), the reference's shapes and dtypes.
+
+    An RQ decomposition of M = P[:, :3] through np.linalg.qr of the row-reversed transpose; the signs are fixed
+    so that diag(K) > 0; when that leaves det(R) < 0, -P (the same camera) is decomposed instead.  The centre
+    is -inv(M) P[:, 3]."""
+    P = np.asarray(P, dtype=np.float64)
+    if P.shape != (3, 4):
+        raise ValueError(f'load_K_Rt_from_P: P must be [3, 4], got {P.shape}')
+
+    def rq(M):
+        q, r = np.linalg.qr(M[::-1].T)          # (J M)^T = q r, J the row reversal
+        K, R = r.T[::-1, ::-1], q.T[::-1]       # M = (J r^T J) (J q^T): upper triangular times orthogonal
+        s = np.where(np.diag(K) < 0, -1.0, 1.0)
+        return K * s[None, :], R * s[:, None]
+    K, R = rq(P[:, :3])
+    if np.linalg.det(R) < 0:
+        K, R = rq(-P[:, :3])
+    intrinsics = np.eye(4)
+    intrinsics[:3, :3] = K / K[2, 2]
+    pose = np.eye(4, dtype=np.float32)
+    pose[:3, :3] = R.T
+    pose[:3, 3] = -np.linalg.solve(P[:, :3], P[:, 3])
+    return intrinsics, pose
+
+
 def gather_rays(src, select_inds):
     """Targets of a random ray batch: torch.gather(src, 1, select_inds[..., None].expand(...)) on the
     device (neus.py:432, :449): src [B, H*W, ...] (rgb, masks), select_inds [B, N] -> [B, N, ...]."""
