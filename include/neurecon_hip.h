@@ -731,11 +731,13 @@ int nr_embed_jvp(const float* x, const float* v, int64_t P, int nfreq, float* ou
 /* the same into rows of ldo >= 3+6F floats, zero beyond the features (the training GEMMs' 16-column blocks) */
 int nr_embed_padded(const float* x, int64_t P, int nfreq, float* out, int ldo, void* stream);
 int nr_embed_jvp_padded(const float* x, const float* v, int64_t P, int nfreq, float* out, int ldo, void* stream);
+/* e0 rows of ld0 >= 3+6F floats; e1 optional (NULL: e0 alone, ld1 / s1 unused), rows of ld1 >= 3+6F */
 int nr_embed_vjp(const float* x, const float* e0, int ld0, const float* e1, int ld1, float s1, int64_t P, int nfreq,
                  float* out, void* stream);
 int nr_softplus100(const float* z, int64_t n, float* h, float* s, void* stream);
 int nr_scale_cols(const float* a, int64_t P, int lda, int col0, int ncols, const float* s, float scale, float* out,
                   void* stream);
+/* hbar rows of ldh >= n floats, the rest [P, n] dense; g and zdot both or neither (NULL: zbar = hbar * s + 0.0) */
 int nr_softplus_adjoint(const float* hbar, int ldh, const float* s, const float* g, const float* zdot, int64_t P,
                         int n, float* zbar, void* stream);
 /* column sums of a row-major [P, n] fp32 matrix (the training path's bias gradients), deterministic

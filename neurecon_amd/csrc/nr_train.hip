@@ -158,9 +158,9 @@ __global__ void softplus_adjoint_kernel(const float* __restrict__ hbar, int ldh,
   const int j = (int)(i - p * n);
   const float si = s[i];
   const float d2 = fmul(fmul(si, fsub(1.0f, si)), 100.0f);  // sigmoid_backward * beta; 0 where s == 1
-  float v = fmul(hbar[p * ldh + j], si);
-  if (g) v = fadd(v, fmul(fmul(g[i], zdot[i]), d2));
-  zbar[i] = v;
+  const float v = fmul(hbar[p * ldh + j], si);
+  // without g the term is +0.0, as a zero g gives it (hbar s = -0.0 becomes +0.0 either way)
+  zbar[i] = fadd(v, g ? fmul(fmul(g[i], zdot[i]), d2) : 0.0f);
 }
 
 // column sums of a row-major [P, n] gradient (bias gradients): block b sums its slab of rows per column
@@ -216,9 +216,8 @@ __global__ void sine_adjoint_kernel(const float* __restrict__ hbar, int ldh, con
   if (i >= P * n) return;
   const int64_t p = i / n;
   const int j = (int)(i - p * n);
-  float v = fmul(hbar[p * ldh + j], s[i]);
-  if (g) v = fadd(v, fmul(fmul(g[i], zdot[i]), fmul(-900.0f, h[i])));
-  zbar[i] = v;
+  const float v = fmul(hbar[p * ldh + j], s[i]);
+  zbar[i] = fadd(v, g ? fmul(fmul(g[i], zdot[i]), fmul(-900.0f, h[i])) : 0.0f);  // without g: + 0.0, as above
 }
 
 __global__ void mul_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n, float* __restrict__ out) {
@@ -1158,7 +1157,10 @@ int nr_embed_jvp_padded(const float* x, const float* v, int64_t P, int nfreq, fl
 
 int nr_embed_vjp(const float* x, const float* e0, int ld0, const float* e1, int ld1, float s1, int64_t P, int nfreq,
                  float* out, void* stream) {
+  const int nf = nfreq < 0 ? 3 : 3 + 6 * nfreq;
   NR_REQUIRE(x && e0 && out && P >= 0 && nfreq <= 10, NR_ERR_ARG, "nr_embed_vjp: bad argument");
+  // a shorter row stride would read the next point's features
+  NR_REQUIRE(ld0 >= nf && (!e1 || ld1 >= nf), NR_ERR_ARG, "nr_embed_vjp: ld0 / ld1 below the feature count");
   if (P == 0) return NR_OK;
   hipLaunchKernelGGL(embed_vjp_kernel, emb_grid(P), dim3(256), 0,
                      (hipStream_t)stream, x, e0, ld0, e1, ld1, s1, P, nfreq, out);

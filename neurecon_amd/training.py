@@ -35,12 +35,14 @@ def _st(t):
 
 
 def _embed(x, nfreq):
+    x = x.contiguous()
     out = torch.empty(x.shape[0], 3 + 6 * nfreq if nfreq >= 0 else 3, device=x.device)
     L.check(L.lib().nr_embed(L.ptr(x), x.shape[0], nfreq, L.ptr(out), _st(x)))
     return out
 
 
 def _softplus(z):
+    z = z.contiguous()    # the kernels take raw pointers: dense rows, shape[1] the leading dimension
     h = torch.empty_like(z)
     s = torch.empty_like(z)
     L.check(L.lib().nr_softplus100(L.ptr(z), z.numel(), L.ptr(h), L.ptr(s), _st(z)))
@@ -49,6 +51,10 @@ def _softplus(z):
 
 def _cols(a, col0, ncols, s=None, scale=1.0):
     """a[:, col0:col0+ncols] * scale (* s), contiguous"""
+    a = a.contiguous()
+    if s is not None:
+        assert s.shape == (a.shape[0], ncols)
+        s = s.contiguous()
     out = torch.empty(a.shape[0], ncols, device=a.device)
     L.check(L.lib().nr_scale_cols(L.ptr(a), a.shape[0], a.shape[1], col0, ncols, L.ptr(s), float(scale), L.ptr(out),
                                   _st(a)))
@@ -56,6 +62,7 @@ def _cols(a, col0, ncols, s=None, scale=1.0):
 
 
 def _sine30(z):
+    z = z.contiguous()
     h = torch.empty_like(z)
     s = torch.empty_like(z)
     L.check(L.lib().nr_sine30(L.ptr(z), z.numel(), L.ptr(h), L.ptr(s), _st(z)))
@@ -148,6 +155,8 @@ def _mm(a, w, bias=None, trans=False, acc32=False):
 
 
 def _mul(a, b):
+    assert a.shape == b.shape
+    a, b = a.contiguous(), b.contiguous()
     out = torch.empty_like(a)
     L.check(L.lib().nr_mul(L.ptr(a), L.ptr(b), a.numel(), L.ptr(out), _st(a)))
     return out

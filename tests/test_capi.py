@@ -260,3 +260,65 @@ def test_adam_optimizer_rejects_cpu_parameters():
     p.grad = torch.ones(4)
     with pytest.raises(RuntimeError, match='GPU'):
         Adam([p]).step()
+
+
+def test_train_elementwise_entries_reject_bad_arguments(lib):
+    """the element-wise training kernels (nr_train.hip) check their arguments before any HIP call: NULL
+    pointers, negative sizes, nfreq > 10, strides below the row (ldo / ld0 / ld1 < nf, ldh < n, col0 +
+    ncols > lda), a bad mode; fake device pointers, only argument sets that return before a launch"""
+    X, V, O, A, B, S, G, Z, H = (0x1000 * k for k in range(1, 10))
+    bad = lambda rc: rc == -1 and 'bad argument' in lib.nr_last_error().decode()
+    # nr_embed / nr_embed_padded / nr_embed_jvp / nr_embed_jvp_padded
+    assert bad(lib.nr_embed(None, 4, 6, O, None)) and bad(lib.nr_embed(X, 4, 6, None, None))
+    assert bad(lib.nr_embed(X, -1, 6, O, None)) and bad(lib.nr_embed(X, 4, 11, O, None))
+    assert bad(lib.nr_embed_padded(X, 4, 6, O, 38, None)) and bad(lib.nr_embed_padded(X, 4, -1, O, 2, None))
+    assert bad(lib.nr_embed_padded(X, 4, 0, O, 2, None)) and bad(lib.nr_embed_padded(None, 4, 6, O, 64, None))
+    assert bad(lib.nr_embed_jvp(None, V, 4, 6, O, None)) and bad(lib.nr_embed_jvp(X, None, 4, 6, O, None))
+    assert bad(lib.nr_embed_jvp(X, V, 4, 6, None, None)) and bad(lib.nr_embed_jvp(X, V, -1, 6, O, None))
+    assert bad(lib.nr_embed_jvp(X, V, 4, 11, O, None)) and bad(lib.nr_embed_jvp_padded(X, V, 4, 10, O, 62, None))
+    # nr_embed_vjp, with the stride checks: ld0 >= nf, and ld1 >= nf when e1 is given
+    vjp = lambda x=X, e0=A, ld0=39, e1=B, ld1=39, P=4, nfreq=6, out=O: \
+        lib.nr_embed_vjp(x, e0, ld0, e1, ld1, 1.0, P, nfreq, out, None)
+    assert bad(vjp(x=None)) and bad(vjp(e0=None)) and bad(vjp(out=None)) and bad(vjp(P=-1)) and bad(vjp(nfreq=11))
+    for kw in (dict(ld0=38), dict(ld1=38), dict(ld0=3), dict(nfreq=-1, ld0=2), dict(nfreq=10, ld0=64, ld1=62)):
+        assert vjp(**kw) == -1 and 'ld0 / ld1' in lib.nr_last_error().decode(), kw
+    assert vjp(P=0) == 0 and vjp(P=0, e1=None, ld1=0) == 0        # e1 NULL: ld1 is not read
+    assert vjp(P=0, ld0=38) == -1                                 # checked before the empty return
+    # nr_softplus100 / nr_sine30 / nr_mul
+    for f in (lib.nr_softplus100, lib.nr_sine30):
+        assert bad(f(None, 8, H, S, None)) and bad(f(Z, 8, None, S, None)) and bad(f(Z, 8, H, None, None))
+        assert bad(f(Z, -1, H, S, None)) and f(Z, 0, H, S, None) == 0
+    assert bad(lib.nr_mul(None, B, 8, O, None)) and bad(lib.nr_mul(A, None, 8, O, None))
+    assert bad(lib.nr_mul(A, B, 8, None, None)) and bad(lib.nr_mul(A, B, -1, O, None))
+    assert lib.nr_mul(A, B, 0, O, None) == 0
+    # nr_scale_cols: the column range lies inside the row
+    sc = lambda a=A, P=4, lda=10, col0=2, ncols=6, out=O: lib.nr_scale_cols(a, P, lda, col0, ncols, None, 1.0, out, None)
+    assert bad(sc(a=None)) and bad(sc(out=None)) and bad(sc(P=-1)) and bad(sc(col0=-1)) and bad(sc(ncols=-1))
+    assert bad(sc(col0=5)) and bad(sc(lda=7))
+    assert sc(P=0) == 0 and sc(ncols=0) == 0
+    # the two adjoints: ldh >= n; g and zdot come together
+    sp = lambda hbar=H, ldh=8, s=S, g=G, zdot=Z, P=4, n=8, out=O: lib.nr_softplus_adjoint(hbar, ldh, s, g, zdot, P, n, out, None)
+    assert bad(sp(hbar=None)) and bad(sp(s=None)) and bad(sp(out=None)) and bad(sp(P=-1)) and bad(sp(n=-1))
+    assert bad(sp(ldh=7)) and bad(sp(g=None)) and bad(sp(zdot=None))
+    assert sp(P=0) == 0 and sp(n=0, ldh=0) == 0 and sp(P=0, g=None, zdot=None) == 0
+    si = lambda hbar=H, ldh=8, s=S, h=A, g=G, zdot=Z, P=4, n=8, out=O: lib.nr_sine_adjoint(hbar, ldh, s, h, g, zdot, P, n, out, None)
+    assert bad(si(hbar=None)) and bad(si(s=None)) and bad(si(h=None)) and bad(si(out=None)) and bad(si(P=-1))
+    assert bad(si(n=-1)) and bad(si(ldh=7)) and bad(si(zdot=None))
+    assert si(P=0) == 0 and si(P=0, g=None, zdot=None) == 0
+    # nr_activation: mode 0..3, g for the two backward modes
+    assert bad(lib.nr_activation(None, G, 8, 0, None)) and bad(lib.nr_activation(A, G, -1, 0, None))
+    assert bad(lib.nr_activation(A, G, 8, 4, None)) and bad(lib.nr_activation(A, G, 8, -1, None))
+    assert bad(lib.nr_activation(A, None, 8, 1, None)) and bad(lib.nr_activation(A, None, 8, 3, None))
+    assert all(lib.nr_activation(A, G, 0, m, None) == 0 for m in range(4)) and lib.nr_activation(A, None, 0, 2, None) == 0
+    # nr_colsum launches even with P = 0: rejecting calls only
+    assert lib.nr_colsum_workspace_bytes(65) == 1024 * 65 * 4
+    cs = lambda a=A, P=8, n=65, out=O, ws=B, nb=1024 * 65 * 4: lib.nr_colsum(a, P, n, out, ws, nb, None)
+    assert bad(cs(a=None)) and bad(cs(out=None)) and bad(cs(P=-1)) and bad(cs(n=0)) and bad(cs(n=-1))
+    assert cs(ws=None) == -4 and 'workspace' in lib.nr_last_error().decode()
+    assert cs(nb=1024 * 65 * 4 - 1) == -4 and cs(n=66) == -4
+    # nr_radiance_input: v and normals with view directions, the feature unless wfeat = 0
+    ri = lambda x=X, v=V, nrm=A, feat=B, P=4, nfv=4, uv=1, wf=256, out=O: \
+        lib.nr_radiance_input(x, v, nrm, feat, P, nfv, uv, wf, out, None)
+    assert bad(ri(x=None)) and bad(ri(out=None)) and bad(ri(v=None)) and bad(ri(nrm=None)) and bad(ri(feat=None))
+    assert bad(ri(P=-1)) and bad(ri(nfv=11)) and bad(ri(wf=-1))
+    assert ri(P=0) == 0 and ri(P=0, uv=0, v=None, nrm=None) == 0 and ri(P=0, wf=0, feat=None) == 0
