@@ -39,6 +39,21 @@ void set_error(const std::string& msg);
     }                                                                                   \
   } while (0)
 
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Workspace carver: take<T>(n) hands out n elements of T at the current offset and advances it to the
+// next 256-byte boundary.  base == nullptr is the sizing pass (null pointers, `off` ends at the total).
+struct Carve {
+  char* base;
+  size_t off;
+  template <class T = float>
+  T* take(size_t n) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off = align256(off + n * sizeof(T));
+    return p;
+  }
+};
+
 // opt-in kernel timing (nr_profile.hip): brackets a launch with events on its stream
 bool prof_on();
 class ProfScope {

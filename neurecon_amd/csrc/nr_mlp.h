@@ -174,5 +174,7 @@ SdfLayout sdf_layout(const NrSdfDesc& d);
 RadLayout rad_layout(const NrRadDesc& d);
 int check_sdf_desc(const NrSdfDesc* d);
 int check_rad_desc(const NrRadDesc* d);
+NerfLayout nerf_layout(const NrNerfDesc& d);
+int check_nerf_desc(const NrNerfDesc* d);
 
 }  // namespace nr

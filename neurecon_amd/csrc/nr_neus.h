@@ -52,21 +52,15 @@ struct NeusOut {
   float* sigma_out; float* radiance_bg;
 };
 
-struct NeusPlan {
-  int64_t Rc;
-  size_t o_ro, o_rd, o_near, o_far, o_dv, o_sv, o_wtmp, o_dnew, o_snew, o_pts, o_mids, o_dmid;
-  size_t o_sdf_f, o_nab_f, o_sdf_m, o_nab_m, o_feat_m, o_rad_m, o_dout, o_x4, o_sigo, o_rado, o_ptsn, o_sn, o_mlp;
-  size_t o_idv, o_nsort, o_dv2, o_sv2, o_idv2;
-  size_t o_slot, o_x4c, o_vdc, o_sigc, o_radc, o_cnt;  // NeRF++: compacted background points
-  size_t o_mslot, o_midc, o_mvd, o_mrad, o_mcnt;        // mid-points of non-zero alpha (compacted)
-  size_t o_slabs, o_tflag, o_tiles, o_tcnt;             // deferred sample nablas
-  size_t total;
+// workspace buffers that only the host orchestration touches (nr_neus.hip neus_bind / neus_chunk)
+struct NeusHost {
+  float* dv2; float* sv2; int* idv2;  // the merges' second sorted lists (ping-pong with dv / sv / idv)
+  int* slot; float* x4c; float* vdc; float* sigc; float* radc; int* cnt;  // NeRF++: compacted background points
+  int* mslot; float* midc; float* mvd; float* mrad; int* mcnt;  // mid-points of non-zero alpha (compacted)
+  void* mlp_ws; size_t mlp_bytes;  // the MLP kernels' reverse-pass scratch: the rest of the workspace
+  bool fused;  // SDF + nablas when a sample is drawn (NeusChunk::nraw)
 };
 
-NeusPlan neus_plan(const NrNeusArgs& a, int64_t Rc);
-// the sample launches defer their reverse pass (see NeusChunk::slabs) for this chunk of R rays
-bool neus_deferred(const NrNeusArgs& a, int64_t R);
-int neus_total_samples(const NrNeusArgs& a);
 __global__ void neus_sample_need(NeusChunk c, const float* s_dev, float s_val);
 __global__ void neus_tile_list(NeusChunk c, int64_t n_tiles);
 __global__ void neus_point_list(NeusChunk c, int64_t n_slots);

@@ -5,9 +5,13 @@
 // and write coalesced lines; the MLP kernels see a flat point list p = sample * Rc + ray.
 // Scans (cumsum / cumprod) accumulate in fp64 exactly like ATen's CPU kernels
 // (acc_type<float, is_cuda=false> = double), each prefix rounded to fp32.
+#include <algorithm>
+#include <cstdint>
+
 #include "nr_common.h"
 #include "nr_mlp.h"
 #include "nr_neus.h"
+#include "nr_render.h"
 
 namespace nr {
 
@@ -1012,90 +1016,415 @@ __global__ void sample_pdf_kernel(const float* __restrict__ bins, const float* _
 }
 
 // ---------------------------------------------------------------------------------------------
-// host orchestration
+// host orchestration: workspace binding, one ray chunk, chunk size, argument checks, entry points
 // ---------------------------------------------------------------------------------------------
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-NeusPlan neus_plan(const NrNeusArgs& a, int64_t Rc) {
-  NeusPlan p{};
-  const bool direct = a.upsample_algo != NR_UPSAMPLE_OFFICIAL;
-  const int n_up0 = a.N_upsample_iters > 0 ? a.N_importance / a.N_upsample_iters : 0;
-  const int S = direct ? a.N_samples + a.N_importance : a.N_samples + a.N_upsample_iters * n_up0;
-  const int n_nog = a.upsample_algo == NR_UPSAMPLE_DIRECT_MORE ? a.N_nograd_samples : 0;
-  p.Rc = Rc;
-  size_t off = 0;
-  auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4); return o; };
-  p.o_ro = take(Rc * 3);
-  p.o_rd = take(Rc * 3);
-  p.o_near = take(Rc);
-  p.o_far = take(Rc);
-  p.o_dv = take((size_t)S * Rc);
-  p.o_sv = take((size_t)S * Rc);
-  p.o_wtmp = take((size_t)(S > n_nog ? S : n_nog) * Rc);
-  const int n_up = direct ? a.N_importance : (a.N_upsample_iters > 0 ? a.N_importance / a.N_upsample_iters : 0);
-  p.o_dnew = take((size_t)(n_up > 0 ? n_up : 1) * Rc);
-  p.o_snew = take((size_t)(n_up > 0 ? n_up : 1) * Rc);
-  p.o_pts = take((size_t)S * Rc * 3);
-  p.o_mids = take((size_t)(S - 1) * Rc * 3);
-  p.o_dmid = take((size_t)(S - 1) * Rc);
-  p.o_sdf_f = take((size_t)S * Rc);
-  p.o_nab_f = take((size_t)S * Rc * 3);
-  p.o_sdf_m = take((size_t)(S - 1) * Rc);
-  p.o_nab_m = take((size_t)(S - 1) * Rc * 3);
-  p.o_feat_m = take((size_t)(S - 1) * Rc * 256);
-  p.o_rad_m = take((size_t)(S - 1) * Rc * 3);
-  const int M = S - 1 + a.N_outside;
-  // weights of all M samples; direct_more also writes its n_nog-1 no-grad weights here first
-  p.o_wtmp = a.N_outside > 0 ? take((size_t)(M > n_nog ? M : n_nog) * Rc) : p.o_wtmp;
-  p.o_dout = take((size_t)(a.N_outside > 0 ? (M > n_nog ? M : n_nog) : (n_nog > 0 ? n_nog : 1)) * Rc);
-  p.o_x4 = take((size_t)(a.N_outside > 0 ? M : 1) * Rc * 4);
-  p.o_sigo = take((size_t)(a.N_outside > 0 ? M : 1) * Rc);
-  p.o_rado = take((size_t)(a.N_outside > 0 ? M : 1) * Rc * 3);
-  const size_t Mo = (size_t)(a.N_outside > 0 ? M : 1) * Rc;
-  p.o_slot = take(Mo);
-  p.o_x4c = take(Mo * 4);
-  p.o_vdc = take(Mo * 3);
-  p.o_sigc = take(Mo);
-  p.o_radc = take(Mo * 3);
-  p.o_cnt = take(1);
-  const size_t Mm = (size_t)(S - 1) * Rc;
-  p.o_mslot = take(Mm);
-  p.o_midc = take(Mm * 3);
-  p.o_mvd = take(Mm * 3);
-  p.o_mrad = take(Mm * 3);
-  p.o_mcnt = take(1);
-  p.o_ptsn = take((size_t)(n_nog > 0 ? n_nog : 1) * Rc * 3);
-  p.o_sn = take((size_t)(n_nog > 0 ? n_nog : 1) * Rc);
-  p.o_idv = take((size_t)S * Rc);
-  p.o_nsort = take((size_t)S * Rc * 3);
-  p.o_dv2 = take((size_t)S * Rc);  // merge ping-pong buffers
-  p.o_sv2 = take((size_t)S * Rc);
-  p.o_idv2 = take((size_t)S * Rc);
-  const size_t tiles = neus_deferred(a, Rc) ? ((size_t)S * Rc + 15) / 16 : 1;
-  p.o_slabs = take(neus_deferred(a, Rc) ? tiles * (kSlabColBytes / 4) : 1);  // 100 KB per 16-slot tile
-  // flags per sample slot; the list (neus_point_list) pads each 1024-slot segment to 16 entries
-  const size_t slots = neus_deferred(a, Rc) ? (size_t)S * Rc : 1;
-  p.o_tflag = take(slots);
-  p.o_tiles = take(slots + 16 * ((slots + 1023) / 1024));
-  p.o_tcnt = take(1);
-  p.o_mlp = off;
-  p.total = off + nr_mlp_workspace_bytes(1);
-  return p;
-}
-
-int neus_total_samples(const NrNeusArgs& a) {
-  const bool direct = a.upsample_algo != NR_UPSAMPLE_OFFICIAL;
-  const int n_up0 = a.N_upsample_iters > 0 ? a.N_importance / a.N_upsample_iters : 0;
-  return direct ? a.N_samples + a.N_importance : a.N_samples + a.N_upsample_iters * n_up0;
-}
-
 // official_solution, render mode without the per-sample nablas (detailed outputs), the f16x3 softplus
 // net, and slots that tile exactly (R % 16 == 0: every launch starts a tile).  With NeRF++ the tiles
 // are flagged after the background net (neus_sample_need_outside); not with its detailed outputs.
-bool neus_deferred(const NrNeusArgs& a, int64_t R) {
+static bool neus_deferred(const NrNeusArgs& a, int64_t R) {
   return a.upsample_algo == NR_UPSAMPLE_OFFICIAL && !a.sample_only && !a.nablas_out && !a.no_mid_skip &&
          !a.no_defer && !(a.N_outside > 0 && (a.sigma_out || a.radiance_bg_out || a.radiance_out)) && a.sdf &&
          a.sdf->precision == NR_PREC_F16X3 && !a.sdf->siren && R > 0 && R % 16 == 0;
 }
 
+// Fills the chunk view `c` (sample counts, workspace pointers) and the host-only buffers `h` for chunks of
+// up to Rc rays carved from `base`, and returns the workspace bytes they need.  base == nullptr sizes only.
+// The arrays are [sample][R] with the chunk's own R, so one binding serves every chunk of a call.
+static size_t neus_bind(const NrNeusArgs& a, int64_t Rc, char* base, NeusChunk& c, NeusHost& h) {
+  const bool direct = a.upsample_algo != NR_UPSAMPLE_OFFICIAL;
+  const int n_up = direct ? 0 : (a.N_upsample_iters > 0 ? a.N_importance / a.N_upsample_iters : 0);
+  c = NeusChunk{};
+  h = NeusHost{};
+  c.N_samples = a.N_samples;
+  c.n_up = n_up;
+  c.n_iters = direct ? 0 : a.N_upsample_iters;
+  c.S = direct ? a.N_samples + a.N_importance : a.N_samples + a.N_upsample_iters * n_up;
+  c.n_imp = a.N_importance;
+  c.n_nog = a.upsample_algo == NR_UPSAMPLE_DIRECT_MORE ? a.N_nograd_samples : 0;
+  c.fixed_s = a.fixed_s;
+  c.t_nog = a.t_nograd;
+  c.N_out = a.N_outside;
+  c.r_obj = a.obj_bounding_radius;
+  c.t_out = a.t_outside;
+  const size_t S = c.S, n_nog = c.n_nog, n_new = direct ? a.N_importance : n_up;
+  Carve cv{base, 0};
+  c.ro = cv.take(Rc * 3);
+  c.rd = cv.take(Rc * 3);
+  c.near = cv.take(Rc);
+  c.far = cv.take(Rc);
+  c.dv = cv.take(S * Rc);
+  c.sv = cv.take(S * Rc);
+  c.wtmp = cv.take(std::max(S, n_nog) * Rc);  // dead when N_outside > 0 (re-carved below); no total may shift
+  c.dnew = cv.take(std::max<size_t>(n_new, 1) * Rc);
+  c.snew = cv.take(std::max<size_t>(n_new, 1) * Rc);
+  c.pts = cv.take(S * Rc * 3);
+  c.mids = cv.take((S - 1) * Rc * 3);
+  c.dmid = cv.take((S - 1) * Rc);
+  c.sdf_f = cv.take(S * Rc);
+  c.nab_f = cv.take(S * Rc * 3);
+  c.sdf_m = cv.take((S - 1) * Rc);
+  c.nab_m = cv.take((S - 1) * Rc * 3);
+  c.feat_m = cv.take((S - 1) * Rc * 256);
+  c.rad_m = cv.take((S - 1) * Rc * 3);
+  const bool bg = a.N_outside > 0;
+  const size_t M = S - 1 + a.N_outside;
+  // weights of all M samples; direct_more also writes its n_nog-1 no-grad weights here first
+  if (bg) c.wtmp = cv.take(std::max(M, n_nog) * Rc);
+  c.d_out = cv.take((bg ? std::max(M, n_nog) : std::max<size_t>(n_nog, 1)) * Rc);
+  const size_t Mo = (bg ? M : 1) * Rc;
+  c.x4 = cv.take(Mo * 4);
+  c.sig_o = cv.take(Mo);
+  c.rad_o = cv.take(Mo * 3);
+  h.slot = cv.take<int>(Mo);  // NeRF++: compacted background points
+  h.x4c = cv.take(Mo * 4);
+  h.vdc = cv.take(Mo * 3);
+  h.sigc = cv.take(Mo);
+  h.radc = cv.take(Mo * 3);
+  h.cnt = cv.take<int>(1);
+  const size_t Mm = (S - 1) * Rc;
+  h.mslot = cv.take<int>(Mm);  // mid-points of non-zero alpha (compacted)
+  h.midc = cv.take(Mm * 3);
+  h.mvd = cv.take(Mm * 3);
+  h.mrad = cv.take(Mm * 3);
+  h.mcnt = cv.take<int>(1);
+  c.pts_nog = cv.take(std::max<size_t>(n_nog, 1) * Rc * 3);
+  c.s_nog = cv.take(std::max<size_t>(n_nog, 1) * Rc);
+  c.idv = cv.take<int>(S * Rc);
+  float* nsort = cv.take(S * Rc * 3);
+  h.dv2 = cv.take(S * Rc);  // merge ping-pong buffers
+  h.sv2 = cv.take(S * Rc);
+  h.idv2 = cv.take<int>(S * Rc);
+  // official_solution evaluates every final sample exactly once, when it is drawn: the coarse and
+  // upsampled points are bit-identical to the final `pts` (neus.py:284 recomputes o + d*dir from
+  // the same depths), so one SDF+nabla launch per round replaces the forward-only round launches
+  // plus the reference's second pass over all samples (neus.py:294).  sdf rides along the sorted
+  // merges (sv); nablas stay in evaluation order (nraw) and are gathered once by neus_points.
+  h.fused = !direct && !a.sample_only;  // the sample pass needs no nablas
+  if (h.fused) {
+    c.nraw = c.nab_f;
+    c.sdf_f = c.sv;
+    c.nab_f = nsort;
+  } else {
+    c.idv = h.idv2 = nullptr;
+  }
+  // deferred sample nablas (NeusChunk::slabs); a chunk that does not defer ignores them
+  const bool defer = neus_deferred(a, Rc);
+  const size_t slots = defer ? S * Rc : 1;
+  c.slabs = cv.take<float4>(defer ? (slots + 15) / 16 * (kSlabColBytes / 16) : 1);  // 100 KB per 16-slot tile
+  // flags per sample slot; the list (neus_point_list) pads each 1024-slot segment to 16 entries
+  c.tflag = cv.take<int>(slots);
+  c.tiles = cv.take<int>(slots + 16 * ((slots + 1023) / 1024));
+  c.tcnt = cv.take<int>(1);
+  h.mlp_ws = base ? base + cv.off : nullptr;
+  h.mlp_bytes = base ? a.workspace_bytes - cv.off : 0;
+  return cv.off + nr_mlp_workspace_bytes(1);
+}
+
+static int neus_chunk(const NrNeusArgs& a, NeusChunk c, const NeusHost& h, int64_t ray0, int R, hipStream_t st) {
+  const bool direct = a.upsample_algo != NR_UPSAMPLE_OFFICIAL, fused = h.fused;
+  const int n_up = c.n_up;
+  c.R = R;
+  // deferred sample nablas (NeusChunk::slabs): sample launches leave per-tile slabs, the reverse pass
+  // runs after the sampling on the tiles of non-zero weight
+  const bool defer = fused && neus_deferred(a, R);
+  if (!defer) {
+    c.slabs = nullptr;
+    c.tflag = c.tiles = c.tcnt = nullptr;
+  }
+  void* const mlp_ws = h.mlp_ws;
+  const size_t mlp_bytes = h.mlp_bytes;
+  const SdfLayout SL = sdf_layout(*a.sdf);
+  const RadLayout RL = rad_layout(*a.rad);
+  // SDF of P sample points at evaluation slot slot0 (coarse: 0; round it: (N_samples + it n_up) R)
+  auto sample_sdf = [&](const float* pts, int64_t P, float* sdf_out, int64_t slot0) -> int {
+    if (defer)
+      return launch_sdf_deferred(SL, a.sdf_packed, pts, P, sdf_out, nullptr, a.sdf->multires,
+                                 (float4*)((char*)c.slabs + (size_t)(slot0 / 16) * kSlabColBytes), nullptr, nullptr,
+                                 1, st);
+    return launch_sdf(SL, a.sdf_packed, pts, P, sdf_out, fused ? c.nraw + slot0 * 3 : nullptr, nullptr,
+                      a.sdf->multires, fused ? mlp_ws : nullptr, fused ? mlp_bytes : 0, st);
+  };
+  const dim3 blk(64), grd((R + 63) / 64);  // one wave per block: a 4096-ray chunk spreads over 64 CUs
+  int rc;
+
+  {
+  ProfScope prof("neus_prologue", (double)R, st);
+  hipLaunchKernelGGL(neus_prologue, grd, blk, 0, st, c, a.rays_o + ray0 * 3, a.rays_d + ray0 * 3, a.t_coarse,
+                     a.obj_bounding_radius, a.near_bypass, a.far_bypass);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  // coarse SDF (no grad, neus.py:220 / :251); direct_more uses its own uniform depths instead
+  if (a.upsample_algo != NR_UPSAMPLE_DIRECT_MORE && (rc = sample_sdf(c.pts, (int64_t)a.N_samples * R, c.sv, 0)))
+    return rc;
+  if (a.upsample_algo == NR_UPSAMPLE_DIRECT_MORE) {  // SDF at N_nograd_samples uniform depths
+    hipLaunchKernelGGL(neus_nograd_points, grd, blk, 0, st, c);
+    NR_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_sdf(SL, a.sdf_packed, c.pts_nog, (int64_t)c.n_nog * R, c.s_nog, nullptr, nullptr,
+                         a.sdf->multires, nullptr, 0, st)))
+      return rc;
+  }
+  if (direct) {
+    ProfScope prof("neus_upsample", (double)R, st);
+    // perturb: this chunk's rows of the caller's [n_rays][N_importance] uniforms
+    const float* u = a.u_rand ? a.u_rand + ray0 * a.N_importance : a.u_fine;
+    hipLaunchKernelGGL(neus_direct_upsample, grd, blk, 0, st, c, (int)(a.upsample_algo == NR_UPSAMPLE_DIRECT_MORE), u,
+                       (int64_t)(a.u_rand ? a.N_importance : 0));
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  // sorted sample lists ping-pong between two buffers; each merge writes the other one
+  float* dvb[2] = {c.dv, h.dv2};
+  float* svb[2] = {c.sv, h.sv2};
+  int* idb[2] = {c.idv, h.idv2};
+  int cur = 0;
+  auto merge = [&](int L) -> int {
+    ProfScope prof("neus_merge", (double)R, st);
+    const int64_t nt = (int64_t)(L + n_up) * R;
+    hipLaunchKernelGGL(neus_merge, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, c, L, dvb[cur ^ 1],
+                       svb[cur ^ 1], idb[cur ^ 1]);
+    cur ^= 1;
+    c.dv = dvb[cur];
+    c.sv = svb[cur];
+    c.idv = idb[cur];
+    if (fused) c.sdf_f = c.sv;
+    NR_HIP_CHECK(hipGetLastError());
+    return NR_OK;
+  };
+  for (int it = 0; it < c.n_iters; ++it) {
+    if (it > 0 && (rc = merge(a.N_samples + (it - 1) * n_up))) return rc;
+    const int64_t slot0 = (int64_t)(a.N_samples + it * n_up) * R;
+    // deferred: every round's points stay at their evaluation slots (the reverse pass reads them)
+    NeusChunk cu = c;
+    if (defer) cu.pts = c.pts + slot0 * 3;
+    {
+      ProfScope prof("neus_upsample", (double)R, st);
+      // perturb: round it's [n_rays][n_up] block of the caller's uniforms
+      const float* u = a.u_rand ? a.u_rand + ((int64_t)it * a.n_rays + ray0) * n_up : a.u_fine;
+      const size_t lds1 = (5 * (size_t)c.S + 1) * sizeof(float);  // four rays per wave when their staging fits
+      if (4 * lds1 <= 65536)
+        hipLaunchKernelGGL((neus_upsample<4>), dim3((unsigned)((R + 3) / 4)), dim3(64), 4 * lds1, st, cu, it, u,
+                           (int64_t)(a.u_rand ? n_up : 0));
+      else
+        hipLaunchKernelGGL((neus_upsample<1>), dim3((unsigned)R), dim3(64), lds1, st, cu, it, u,
+                           (int64_t)(a.u_rand ? n_up : 0));
+    }
+    NR_HIP_CHECK(hipGetLastError());
+    if ((rc = sample_sdf(cu.pts, (int64_t)n_up * R, c.snew, slot0))) return rc;
+  }
+  if (c.n_iters > 0 && (rc = merge(c.S - n_up))) return rc;
+  if (defer) {  // nablas of the tiles holding a sample of non-zero interval weight; the rest stay 0
+    const int64_t nslot = (int64_t)c.S * R;
+    c.tshift = 0;  // flags per sample slot, the reverse pass on the listed samples (sdf4_kernel STAGE 4)
+    NR_HIP_CHECK(hipMemsetAsync(c.nraw, 0, (size_t)nslot * 3 * sizeof(float), st));
+    if (a.calc_normal && a.N_outside == 0) {  // normals_volume is the only reader of the sample nablas here
+      // (with NeRF++ the flags need the background's alphas: after the background net, below)
+      NR_HIP_CHECK(hipMemsetAsync(c.tflag, 0, (size_t)nslot * sizeof(int), st));
+      NR_HIP_CHECK(hipMemsetAsync(c.tcnt, 0, sizeof(int), st));
+      const int64_t nq = (int64_t)(c.S - 1) * R;
+      hipLaunchKernelGGL(neus_sample_need, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, c, a.s_dev, a.s);
+      NR_HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(neus_point_list, dim3((unsigned)((nslot + 1023) / 1024)), dim3(1024), 0, st, c, nslot);
+      NR_HIP_CHECK(hipGetLastError());
+      if ((rc = launch_sdf_deferred(SL, a.sdf_packed, c.pts, nslot, nullptr, c.nraw, a.sdf->multires, c.slabs, c.tiles,
+                                    c.tcnt, 4, st)))
+        return rc;
+    }
+  }
+  if (a.sample_only) {  // training: the sorted depths are the whole output (neus.py:279)
+    hipLaunchKernelGGL(neus_write_dall, dim3((unsigned)(((int64_t)c.S * R + 255) / 256)), dim3(256), 0, st, c.dv,
+                       (int64_t)R, c.S, ray0, a.d_all_out);
+    NR_HIP_CHECK(hipGetLastError());
+    return NR_OK;
+  }
+  {
+    ProfScope prof("neus_points", (double)R, st);
+    hipLaunchKernelGGL(neus_expand, dim3((unsigned)(((int64_t)c.S * R + 255) / 256)), dim3(256), 0, st, c,
+                       (int)!(defer && a.N_outside > 0));
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  // SDF + nablas at the samples (neus.py:294); already in sv / nv on the fused path
+  if (!fused && (rc = launch_sdf(SL, a.sdf_packed, c.pts, (int64_t)c.S * R, c.sdf_f, c.nab_f, nullptr,
+                                 a.sdf->multires, mlp_ws, mlp_bytes, st)))
+    return rc;
+  // SDF + nablas + geometry feature at the mid-points, then the radiance net (neus.py:103-106, :298)
+  const int64_t Pm = (int64_t)(c.S - 1) * R;
+  // with a fold pack, feat_m carries u (F8' in F8's place) and the radiance net's layer 0 is R0'
+  const char* f8p = nullptr;
+  const char* r0p = nullptr;
+  if (a.fold_packed) {
+    const FoldLayout FL = fold_layout(RL);
+    f8p = (const char*)a.fold_packed + FL.f8_off;
+    r0p = (const char*)a.fold_packed + FL.r0_off;
+  }
+  if (a.radiance_out || a.no_mid_skip) {  // every mid-point, as the reference
+    if ((rc = launch_sdf(SL, a.sdf_packed, c.mids, Pm, c.sdf_m, c.nab_m, c.feat_m, a.sdf->multires, mlp_ws, mlp_bytes,
+                         st, nullptr, 0, f8p)))
+      return rc;
+    if ((rc = launch_radiance(RL, a.rad_packed, c.mids, c.rd, 1, R, c.nab_m, c.feat_m, Pm, c.rad_m,
+                              a.rad->multires_view, st, nullptr, r0p)))
+      return rc;
+  } else {  // only the mid-points whose alpha is not exactly 0 (neus_mid_compact); bit-identical maps
+    NR_HIP_CHECK(hipMemsetAsync(h.mcnt, 0, sizeof(int), st));
+    const dim3 g1((unsigned)((Pm + 255) / 256));
+    hipLaunchKernelGGL(neus_mid_compact, dim3((unsigned)((Pm + 1023) / 1024)), dim3(1024), 0, st, c, a.s_dev, a.s,
+                       h.mcnt, h.mslot, h.midc, h.mvd);
+    NR_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_sdf(SL, a.sdf_packed, h.midc, Pm, c.sdf_m, c.nab_m, c.feat_m, a.sdf->multires, mlp_ws, mlp_bytes,
+                         st, h.mcnt, 1, f8p)))
+      return rc;
+    if ((rc = launch_radiance(RL, a.rad_packed, h.midc, h.mvd, 1, INT64_MAX, c.nab_m, c.feat_m, Pm, h.mrad,
+                              a.rad->multires_view, st, h.mcnt, r0p)))
+      return rc;
+    hipLaunchKernelGGL(neus_mid_scatter, g1, dim3(256), 0, st, h.mslot, h.mrad, Pm, c.rad_m);
+    NR_HIP_CHECK(hipGetLastError());
+  }
+  NeusOut o{ray0, a.rgb, a.depth, a.acc, a.normals, a.d_final, a.sdf_out, a.nablas_out,
+            a.radiance_out, a.alpha_out, a.cdf_out, a.weights_out, a.sigma_out, a.radiance_bg_out};
+  if (a.N_outside > 0) {  // NeRF++ background on [mid-points ; inverted-sphere samples]
+    hipLaunchKernelGGL(neus_outside_points, grd, blk, 0, st, c,
+                       a.t_out_rand ? a.t_out_rand + ray0 * a.N_outside : (const float*)nullptr);
+    NR_HIP_CHECK(hipGetLastError());
+    const int64_t Po = (int64_t)(c.S - 1 + a.N_outside) * R;
+    if (a.sigma_out || a.radiance_bg_out) {  // detailed outputs: the background at every sample, as the reference
+      if ((rc = launch_nerf(nerf_layout(*a.nerf), a.nerf_packed, c.x4, c.rd, 1, R, Po, c.sig_o, c.rad_o, st)))
+        return rc;
+    } else {  // only the background values the compositing reads (neus_outside_compact)
+      NR_HIP_CHECK(hipMemsetAsync(h.cnt, 0, sizeof(int), st));
+      const dim3 g1((unsigned)((Po + 255) / 256));
+      hipLaunchKernelGGL(neus_outside_compact, dim3((unsigned)((Po + 1023) / 1024)), dim3(1024), 0, st, c, h.cnt,
+                         h.slot, h.x4c, h.vdc);
+      NR_HIP_CHECK(hipGetLastError());
+      if ((rc = launch_nerf(nerf_layout(*a.nerf), a.nerf_packed, h.x4c, h.vdc, 1, INT64_MAX, Po, h.sigc, h.radc, st,
+                            h.cnt)))
+        return rc;
+      hipLaunchKernelGGL(neus_outside_scatter, g1, dim3(256), 0, st, h.slot, h.sigc, h.radc, Po, c.sig_o, c.rad_o);
+      NR_HIP_CHECK(hipGetLastError());
+    }
+    if (defer) {  // deferred sample nablas: samples (or tiles) whose (inside or background) alpha != 0
+      const int64_t nslot = (int64_t)c.S * R;
+      c.tshift = 0;
+      if (a.calc_normal) {
+        NR_HIP_CHECK(hipMemsetAsync(c.tflag, 0, (size_t)nslot * sizeof(int), st));
+        NR_HIP_CHECK(hipMemsetAsync(c.tcnt, 0, sizeof(int), st));
+        hipLaunchKernelGGL(neus_sample_need_outside, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, st, c,
+                           a.s_dev, a.s);
+        NR_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(neus_point_list, dim3((unsigned)((nslot + 1023) / 1024)), dim3(1024), 0, st, c, nslot);
+        NR_HIP_CHECK(hipGetLastError());
+        if ((rc = launch_sdf_deferred(SL, a.sdf_packed, c.pts, nslot, nullptr, c.nraw, a.sdf->multires, c.slabs,
+                                      c.tiles, c.tcnt, 4, st)))
+          return rc;
+      }
+      hipLaunchKernelGGL(neus_gather_nablas, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, st, c);
+      NR_HIP_CHECK(hipGetLastError());
+    }
+    ProfScope prof("neus_composite", (double)R, st);
+    const int M = c.S - 1 + a.N_outside;
+    const size_t lds1 = (6 * (size_t)M + 4 * (size_t)c.S) * sizeof(float);  // wave-per-ray staging of one ray
+    if (4 * lds1 <= 65536)
+      hipLaunchKernelGGL((neus_composite_outside_w<4>), dim3((unsigned)((R + 3) / 4)), dim3(64), 4 * lds1, st, c, o,
+                         a.s_dev, a.s, a.calc_normal, a.white_bkgd);
+    else if (lds1 <= 65536)
+      hipLaunchKernelGGL((neus_composite_outside_w<1>), dim3((unsigned)R), dim3(64), lds1, st, c, o, a.s_dev, a.s,
+                         a.calc_normal, a.white_bkgd);
+    else
+      hipLaunchKernelGGL(neus_composite_outside, grd, blk, 0, st, c, o, a.s_dev, a.s, a.calc_normal, a.white_bkgd);
+  } else {
+    ProfScope prof("neus_composite", (double)R, st);
+    const size_t lds1 = 9 * (size_t)c.S * sizeof(float);  // four rays per wave when four rays' staging fits
+    if (4 * lds1 <= 65536)  // the dynamic-LDS limit per workgroup (nr_neus_render checks lds1 against it)
+      hipLaunchKernelGGL((neus_composite<4>), dim3((unsigned)((R + 3) / 4)), dim3(64), 4 * lds1, st, c, o, a.s_dev, a.s,
+                         a.calc_normal, a.white_bkgd);
+    else
+      hipLaunchKernelGGL((neus_composite<1>), dim3((unsigned)R), dim3(64), lds1, st, c, o, a.s_dev, a.s, a.calc_normal,
+                         a.white_bkgd);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  return NR_OK;
+}
+
+// rays per chunk: at most 16384, the caller's max_chunk_rays (its rayschunk) -- with no explicit
+// workspace budget a hint floored at NR_MIN_CHUNK_RAYS (the reference's validation rayschunk of 256
+// would leave the per-ray kernels a few CUs; memory is bounded by the default budget), exact when the
+// caller also set max_workspace_bytes -- and as many as keep the workspace within
+// max_workspace_bytes (the binding is affine in the chunk's ray count); deferred chunks (8 KB of slabs
+// per sample) are a multiple of 16 rays, so that every launch starts a tile
+static int64_t neus_chunk_rays(const NrNeusArgs* a) {
+  const int64_t n = a->n_rays > 0 ? a->n_rays : 1;
+  int64_t cap = 16384;
+  // the floor applies to a caller that left the memory bound to the library (max_workspace_bytes 0); one
+  // that set a workspace budget gets its max_chunk_rays exactly, as the reference's rayschunk loop
+  if (a->max_chunk_rays > 0)
+    cap = std::min(cap, a->max_workspace_bytes ? a->max_chunk_rays : std::max<int64_t>(a->max_chunk_rays, NR_MIN_CHUNK_RAYS));
+  const size_t budget = a->max_workspace_bytes ? a->max_workspace_bytes : NR_DEFAULT_WORKSPACE_BYTES;
+  const bool defer = neus_deferred(*a, 16);
+  NeusChunk c;
+  NeusHost h;  // two sizing passes, deferral decided as for a 16-ray-multiple chunk
+  const size_t t1 = neus_bind(*a, 1024, nullptr, c, h), t2 = neus_bind(*a, 2048, nullptr, c, h);
+  const size_t per_ray = (t2 - t1) / 1024 + 1, fixed = t1 > 1024 * per_ray ? t1 - 1024 * per_ray : 0;
+  const int64_t fit = budget > fixed ? (int64_t)((budget - fixed) / per_ray) : 0;
+  cap = std::min(cap, std::max<int64_t>(fit, 16));
+  // deferred chunks tile exactly: a ray count that is not a multiple of 16 renders as 16-multiple
+  // chunks (deferred) plus a < 16-ray tail (nablas when drawn)
+  if (defer && n > 16 && n % 16) cap = std::min(cap, n / 16 * 16);
+  if (n <= cap) return n;
+  if (defer && cap >= 16) cap = cap / 16 * 16;
+  return std::max<int64_t>(cap, 1);
+}
+
+static int check_neus(const NrNeusArgs* a) {
+  static const char* const kName = "nr_neus_render";
+  int rc = check_render_common(kName, a);
+  if (rc) return rc;
+  NR_REQUIRE(a->sdf_packed && a->rad && (a->rad_packed || a->sample_only) && a->t_coarse, NR_ERR_ARG,
+             "nr_neus_render: null argument");
+  NR_REQUIRE(!a->fold_packed || fold_applies(*a->sdf, *a->rad), NR_ERR_ARG,
+             "nr_neus_render: a fold pack needs the f16x3 softplus SDF net and a f16x3 ReLU D=4 radiance net");
+  NR_REQUIRE(a->N_samples >= 2, NR_ERR_ARG, "nr_neus_render: N_samples must be >= 2");
+  if ((rc = check_render_normals(kName, a))) return rc;
+  NR_REQUIRE(a->N_outside >= 0, NR_ERR_ARG, "nr_neus_render: N_outside must be >= 0");
+  if (a->N_outside > 0) {
+    if ((rc = check_nerf_desc(a->nerf))) return rc;
+    NR_REQUIRE(a->nerf_packed && a->t_outside, NR_ERR_ARG, "nr_neus_render: N_outside > 0 needs the NeRF++ net");
+  }
+  NR_REQUIRE(a->upsample_algo >= NR_UPSAMPLE_OFFICIAL && a->upsample_algo <= NR_UPSAMPLE_DIRECT_MORE, NR_ERR_ARG,
+             "nr_neus_render: unknown upsample_algo");
+  if (a->upsample_algo != NR_UPSAMPLE_OFFICIAL) {
+    NR_REQUIRE(a->N_importance >= 1 && a->u_fine && a->fixed_s > 0.f, NR_ERR_ARG,
+               "nr_neus_render: direct upsampling needs N_importance >= 1, u_fine and fixed_s > 0");
+    NR_REQUIRE(a->upsample_algo != NR_UPSAMPLE_DIRECT_MORE || (a->N_nograd_samples >= 2 && a->t_nograd), NR_ERR_ARG,
+               "nr_neus_render: direct_more needs N_nograd_samples >= 2 and t_nograd");
+  } else if (a->N_upsample_iters > 0) {
+    const int n_up = a->N_importance / a->N_upsample_iters;
+    NR_REQUIRE(n_up >= 1 && n_up <= kMaxUp && a->u_fine, NR_ERR_UNSUPPORTED,
+               "nr_neus_render: N_importance/N_upsample_iters must be in [1, 32]");
+  }
+  return NR_OK;
+}
+
 }  // namespace nr
+
+using namespace nr;
+
+extern "C" size_t nr_neus_workspace_bytes(const NrNeusArgs* a) {
+  if (!a) return 0;
+  NeusChunk c;
+  NeusHost h;
+  return neus_bind(*a, neus_chunk_rays(a), nullptr, c, h);
+}
+
+extern "C" int nr_neus_render(const NrNeusArgs* a, void* stream) {
+  int rc = check_neus(a);
+  if (rc || a->n_rays <= 0) return rc;
+  const int64_t Rc = neus_chunk_rays(a);
+  NeusChunk c;
+  NeusHost h;
+  const size_t total = neus_bind(*a, Rc, (char*)a->workspace, c, h);
+  NR_REQUIRE(a->workspace && a->workspace_bytes >= total, NR_ERR_WORKSPACE, "nr_neus_render: workspace too small");
+  // the wave-per-ray upsampling / compositing kernels stage S samples per ray in LDS
+  size_t lds_max;
+  if ((rc = lds_limit(lds_max))) return rc;
+  NR_REQUIRE((size_t)9 * c.S * sizeof(float) <= lds_max, NR_ERR_UNSUPPORTED,
+             "nr_neus_render: N_samples + N_importance too large for the per-ray LDS staging of the compositing");
+  return for_chunks(a->n_rays, Rc, [&](int64_t r0, int R) { return neus_chunk(*a, c, h, r0, R, (hipStream_t)stream); });
+}
+

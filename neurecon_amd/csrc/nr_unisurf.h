@@ -55,20 +55,11 @@ struct UniOut {
 constexpr int kMarchK = 32;
 constexpr int kWinSlices = 64;  // blocks per F.normalize window in its sum of squares
 
-struct UniPlan {
-  int64_t Rc;
-  size_t o_ro, o_rd, o_near, o_far, o_thr, o_ptsm, o_sm, o_sec, o_ptss, o_ss, o_dall, o_ptsf, o_sdff, o_nabf;
-  size_t o_featf, o_nrmf, o_radf, o_wss, o_wsp, o_mlp;
-  size_t o_act0, o_act1, o_acnt, o_ptsc, o_sc;  // chunked march: active lists, counts, compacted points / sdf
-  size_t total;
-  int64_t max_windows;
+// workspace buffers that only the host orchestration touches (nr_unisurf.hip unisurf_bind / unisurf_chunk)
+struct UniHost {
+  int* act0; int* act1; int* acnt; float* ptsc; float* sc;  // run_march's lists, counts, compacted points / sdf
+  void* mlp_ws; size_t mlp_bytes;  // the MLP kernels' reverse-pass scratch: the rest of the workspace
 };
-
-UniPlan unisurf_plan(const NrUnisurfArgs& a, int64_t Rc);
-int64_t unisurf_chunk_rays(const NrUnisurfArgs& a);
-// window geometry of one batch row of the whole batch: (rayschunk clipped, windows per full chunk,
-// windows per row)
-void unisurf_windows(const NrUnisurfArgs& a, int64_t& rc_rays, int64_t& nw_full, int64_t& nw_row);
 
 __global__ void uni_prologue(UniChunk c, const float* rays_o, const float* rays_d);
 __global__ void uni_root(UniChunk c);

@@ -6,8 +6,12 @@
 // F.normalize(nablas) with torch's default dim=1 to the radiance net (unisurf.py:36): for batched
 // renders that normalises each gradient component over a whole batchify_query chunk of points
 // (train_util.py:23-71), which is reproduced here with a per-window fp64 reduction.
+#include <algorithm>
+
 #include "nr_common.h"
 #include "nr_mlp.h"
+#include "nr_neus.h"
+#include "nr_render.h"
 #include "nr_unisurf.h"
 
 namespace nr {
@@ -450,15 +454,13 @@ __global__ void uni_composite(UniChunk c, UniOut o, int calc_normal, int white_b
 }
 
 // ---------------------------------------------------------------------------------------------
-// workspace plan and chunking
+// host orchestration: chunking, workspace binding, the march, one ray chunk, argument checks, entry points
 // ---------------------------------------------------------------------------------------------
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static constexpr int64_t kUniMaxChunk = 65536;
 
 // rays per internal chunk: in window mode (batched call) a chunk never straddles a normalisation
 // window, i.e. it is the reference's ray chunk (rayschunk) or a whole number of windows of it
-int64_t unisurf_chunk_rays(const NrUnisurfArgs& a) {
+static int64_t unisurf_chunk_rays(const NrUnisurfArgs& a) {
   const int64_t P = a.N_query + a.N_freespace;
   if (a.normal_mode == 1 && a.shard_row_rays > 0)  // a multi-GPU shard is one chunk
     return a.n_rays <= kUniMaxChunk ? (a.n_rays > 0 ? a.n_rays : 1) : -1;
@@ -474,7 +476,7 @@ int64_t unisurf_chunk_rays(const NrUnisurfArgs& a) {
   return a.n_rays < kUniMaxChunk ? (a.n_rays > 0 ? a.n_rays : 1) : kUniMaxChunk;
 }
 
-void unisurf_windows(const NrUnisurfArgs& a, int64_t& rc_rays, int64_t& nw_full, int64_t& nw_row) {
+static void unisurf_windows(const NrUnisurfArgs& a, int64_t& rc_rays, int64_t& nw_full, int64_t& nw_row) {
   const int64_t P = a.N_query + a.N_freespace;
   const int64_t row = a.shard_row_rays > 0 ? a.shard_row_rays : (a.rays_per_batch > 0 ? a.rays_per_batch : a.n_rays);
   const int64_t nc = a.netchunk > 0 ? a.netchunk : 1;
@@ -485,45 +487,64 @@ void unisurf_windows(const NrUnisurfArgs& a, int64_t& rc_rays, int64_t& nw_full,
   if (nw_row < 1) nw_row = 1;
 }
 
-UniPlan unisurf_plan(const NrUnisurfArgs& a, int64_t Rc) {
-  UniPlan p{};
-  const int P = a.N_query + a.N_freespace;
-  p.Rc = Rc;
-  int64_t rc_rays = 1, nw_full = 1, nw_row = 1;
-  if (a.normal_mode == 1) unisurf_windows(a, rc_rays, nw_full, nw_row);
-  p.max_windows = nw_row;  // one batch row's windows (internal chunks never span rows)
-  size_t off = 0;
-  auto take = [&](size_t words) { size_t o = off; off = align_up(off + words * 4); return o; };
-  p.o_ro = take(Rc * 3);
-  p.o_rd = take(Rc * 3);
-  p.o_near = take(Rc);
-  p.o_far = take(Rc);
-  p.o_thr = take(Rc);
-  p.o_ptsm = take((size_t)a.N_steps * Rc * 3);
-  p.o_sm = take((size_t)a.N_steps * Rc);
-  p.o_sec = take((size_t)Rc * 9);
-  p.o_ptss = take(Rc * 3);
-  p.o_ss = take(Rc);
-  p.o_dall = take((size_t)P * Rc);
-  p.o_ptsf = take((size_t)P * Rc * 3);
-  p.o_sdff = take((size_t)P * Rc);
-  p.o_nabf = take((size_t)P * Rc * 3);
-  p.o_featf = take((size_t)P * Rc * 256);
-  p.o_nrmf = take((size_t)P * Rc * 3);
-  p.o_radf = take((size_t)P * Rc * 3);
-  p.o_wss = take((size_t)p.max_windows * 6);
+// Fills the chunk view `c` (sampling constants, window geometry, workspace pointers) and the host-only
+// buffers `h` for chunks of up to Rc rays carved from `base`; returns the workspace bytes.  base == nullptr
+// sizes only.
+static size_t unisurf_bind(const NrUnisurfArgs& a, int64_t Rc, char* base, UniChunk& c, UniHost& h) {
+  c = UniChunk{};
+  c.N_steps = a.N_steps;
+  c.N_query = a.N_query;
+  c.N_free = a.N_freespace;
+  c.P = a.N_query + a.N_freespace;
+  c.logit_tau = a.logit_tau;
+  c.interval = a.interval;
+  c.too_close = a.too_close_threshold;
+  c.near_bypass = a.near_bypass;
+  c.far_bypass = a.far_bypass;
+  c.r_interest = a.radius_of_interest;
+  c.netchunk = a.netchunk;
+  c.t_march = a.t_march; c.t_query = a.t_query; c.t_free = a.t_free;
+  c.no_secant = a.no_secant;
+  const bool sharded = a.normal_mode == 1 && a.shard_row_rays > 0;
+  int64_t nw_row = 1;  // one batch row's windows (internal chunks never span rows)
+  if (a.normal_mode == 1) {
+    unisurf_windows(a, c.rc_rays, c.nw_full, c.nw_row);
+    c.row_rays = sharded ? a.shard_row_rays : (a.rays_per_batch > 0 ? a.rays_per_batch : a.n_rays);
+    nw_row = c.nw_row;
+  }
+  const size_t P = c.P;
+  Carve cv{base, 0};
+  c.ro = cv.take(Rc * 3);
+  c.rd = cv.take(Rc * 3);
+  c.near = cv.take(Rc);
+  c.far = cv.take(Rc);
+  c.thr = cv.take(Rc);
+  c.pts_m = cv.take((size_t)a.N_steps * Rc * 3);
+  c.sm = cv.take((size_t)a.N_steps * Rc);
+  c.sec = cv.take((size_t)Rc * 9);
+  c.pts_s = cv.take(Rc * 3);
+  c.ss = cv.take(Rc);
+  c.d_all = cv.take(P * Rc);
+  c.pts_f = cv.take(P * Rc * 3);
+  c.sdf_f = cv.take(P * Rc);
+  c.nab_f = cv.take(P * Rc * 3);
+  c.feat_f = cv.take(P * Rc * 256);
+  c.nrm_f = cv.take(P * Rc * 3);
+  c.rad_f = cv.take(P * Rc * 3);
+  c.wss = cv.take<double>((size_t)nw_row * 3);
+  if (sharded) c.wss = a.window_ss;  // the caller's [B][nw_row][3], all-reduced by window_reduce
   // a multi-GPU shard renders all its batch rows in one chunk (nr_unisurf_render), internal chunks one row
   const int64_t nloc = a.rays_per_batch > 0 ? a.rays_per_batch : (a.n_rays > 0 ? a.n_rays : 1);
-  const int64_t rows = (a.normal_mode == 1 && a.shard_row_rays > 0) ? (a.n_rays + nloc - 1) / nloc : 1;
-  p.o_wsp = take((size_t)(rows > 0 ? rows : 1) * p.max_windows * kWinSlices * 6);
-  p.o_act0 = take(Rc);
-  p.o_act1 = take(Rc);
-  p.o_acnt = take(2);
-  p.o_ptsc = take((size_t)kMarchK * Rc * 3);
-  p.o_sc = take((size_t)kMarchK * Rc);
-  p.o_mlp = off;
-  p.total = off + nr_mlp_workspace_bytes(1);
-  return p;
+  const int64_t rows = sharded ? (a.n_rays + nloc - 1) / nloc : 1;
+  c.wsp = cv.take<double>((size_t)(rows > 0 ? rows : 1) * nw_row * kWinSlices * 3);
+  h.act0 = cv.take<int>(Rc);  // chunked march: active lists, counts, compacted points / sdf
+  h.act1 = cv.take<int>(Rc);
+  h.acnt = cv.take<int>(2);
+  h.ptsc = cv.take((size_t)kMarchK * Rc * 3);
+  h.sc = cv.take((size_t)kMarchK * Rc);
+  h.mlp_ws = base ? base + cv.off : nullptr;
+  h.mlp_bytes = base ? a.workspace_bytes - cv.off : 0;
+  return cv.off + nr_mlp_workspace_bytes(1);
 }
 
 int run_march(const SdfLayout& SL, const void* packed, int multires, const UniChunk& c, bool full, int* act0,
@@ -559,4 +580,153 @@ int run_march(const SdfLayout& SL, const void* packed, int multires, const UniCh
   return NR_OK;
 }
 
+// One chunk (unisurf.py:118-244): prologue -> SDF(march) -> root -> [SDF(secant point) -> secant] x
+// N_secant_steps -> samples -> SDF+nablas+feature -> F.normalize -> radiance -> composite.
+// rays [ray0, ray0 + R) of the call = `R / nloc` batch rows of nloc rays, starting at row-relative
+// ray row_ray0 (internal chunks: one row; a multi-GPU shard: all of its rows in one chunk)
+static int unisurf_chunk(const NrUnisurfArgs& a, UniChunk c, const UniHost& h, int64_t ray0, int R, int64_t row_ray0,
+                         int nloc, hipStream_t st) {
+  c.R = R;
+  if (a.normal_mode == 1) {
+    c.row_ray0 = row_ray0;
+    c.nloc = nloc;
+  }
+  c.u_q = a.u_query ? a.u_query + ray0 * a.N_query : nullptr;
+  c.u_f = a.u_free ? a.u_free + ray0 * a.N_freespace : nullptr;
+  const SdfLayout SL = sdf_layout(*a.sdf);
+  const RadLayout RL = rad_layout(*a.rad);
+  const dim3 blk(64), grd((R + 63) / 64);  // one wave per block: a 4096-ray chunk spreads over 64 CUs
+  const int64_t P = (int64_t)c.P * R;
+  int rc;
+  {
+    ProfScope prof("unisurf_prologue", (double)R, st);
+    hipLaunchKernelGGL(uni_prologue, grd, blk, 0, st, c, a.rays_o + ray0 * 3, a.rays_d + ray0 * 3);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  // the march (ray_casting.py:88-101) in chunks of kMarchK steps over the rays still without a crossing
+  // (full_march: every step of every ray in one launch, the bit-identity test's reference)
+  if ((rc = run_march(SL, a.sdf_packed, a.sdf->multires, c, a.full_march != 0, h.act0, h.act1, h.acnt, h.ptsc, h.sc,
+                      st)))
+    return rc;
+  hipLaunchKernelGGL(uni_root, grd, blk, 0, st, c);
+  NR_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < (a.no_secant ? 0 : a.N_secant_steps); ++i) {
+    if ((rc = launch_sdf(SL, a.sdf_packed, c.pts_s, R, c.ss, nullptr, nullptr, a.sdf->multires, nullptr, 0, st)))
+      return rc;
+    hipLaunchKernelGGL(uni_secant, grd, blk, 0, st, c, (int)(i == a.N_secant_steps - 1));
+    NR_HIP_CHECK(hipGetLastError());
+  }
+  UniOut o{ray0, a.rgb, a.depth, a.acc, a.normals, a.surface_points, a.mask_surface, a.depth_surface,
+           a.radiance_out, a.sdf_out, a.nablas_out, a.alpha_out, a.weights_out};
+  hipLaunchKernelGGL(uni_samples, grd, blk, 0, st, c, o);
+  NR_HIP_CHECK(hipGetLastError());
+  if (a.d_all_out) {  // training: the sorted sample depths, ray-major (unisurf.py:201)
+    hipLaunchKernelGGL(neus_write_dall, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c.d_all, (int64_t)R, c.P,
+                       ray0, a.d_all_out);
+    NR_HIP_CHECK(hipGetLastError());
+  }
+  if (a.sample_only) return NR_OK;
+  if ((rc = launch_sdf(SL, a.sdf_packed, c.pts_f, P, c.sdf_f, c.nab_f, c.feat_f, a.sdf->multires, h.mlp_ws,
+                       h.mlp_bytes, st)))
+    return rc;
+  if (a.normal_mode == 1) {
+    hipLaunchKernelGGL(uni_window_ss_part, dim3((unsigned)c.nw_row, (unsigned)(R / nloc), kWinSlices), dim3(256), 0,
+                       st, c);
+    NR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(uni_window_ss_sum, dim3((unsigned)c.nw_row, (unsigned)(R / nloc)), dim3(64), 0, st, c);
+    NR_HIP_CHECK(hipGetLastError());
+    if (a.shard_row_rays > 0) {  // every rank's partial sums -> the sums of the whole batch (collective, stream-ordered)
+      const int rr = a.window_reduce(a.window_user);
+      NR_REQUIRE(rr == 0, NR_ERR_ARG, "nr_unisurf_render: window_reduce callback failed");
+    }
+  }
+  hipLaunchKernelGGL(uni_normalize, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c, a.normal_mode);
+  NR_HIP_CHECK(hipGetLastError());
+  if ((rc = launch_radiance(RL, a.rad_packed, c.pts_f, c.rd, 1, R, c.nrm_f, c.feat_f, P, c.rad_f,
+                            a.rad->multires_view, st)))
+    return rc;
+  {
+    ProfScope prof("unisurf_composite", (double)R, st);
+    hipLaunchKernelGGL(uni_composite, grd, blk, 0, st, c, o, a.calc_normal, a.white_bkgd);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  return NR_OK;
+}
+
+static int check_unisurf(const NrUnisurfArgs* a) {
+  static const char* const kName = "nr_unisurf_render";
+  int rc = check_render_common(kName, a);
+  if (rc) return rc;
+  NR_REQUIRE(!a->sample_only || a->shard_row_rays <= 0, NR_ERR_ARG,
+             "nr_unisurf_render: sample_only is not a sharded render");
+  NR_REQUIRE(a->sdf_packed && a->rad && (a->rad_packed || a->sample_only) && a->t_march && a->t_query && a->t_free,
+             NR_ERR_ARG, "nr_unisurf_render: null argument");
+  if ((rc = check_render_normals(kName, a))) return rc;
+  NR_REQUIRE(a->N_steps >= 2 && a->N_secant_steps >= 0 && a->N_query >= 1 && a->N_freespace >= 1, NR_ERR_ARG,
+             "nr_unisurf_render: bad sample counts");
+  NR_REQUIRE(a->normal_mode == 0 || a->normal_mode == 1, NR_ERR_ARG, "nr_unisurf_render: normal_mode must be 0|1");
+  NR_REQUIRE(!a->u_query == !a->u_free, NR_ERR_ARG, "nr_unisurf_render: u_query and u_free go together");
+  NR_REQUIRE(a->normal_mode == 0 || (a->rayschunk > 0 && a->netchunk > 0), NR_ERR_ARG,
+             "nr_unisurf_render: rayschunk/netchunk must be positive");
+  if (a->rays_per_batch > 0)
+    NR_REQUIRE(a->n_rays % a->rays_per_batch == 0, NR_ERR_ARG, "nr_unisurf_render: n_rays % rays_per_batch != 0");
+  NR_REQUIRE(unisurf_chunk_rays(*a) > 0, NR_ERR_UNSUPPORTED,
+             "nr_unisurf_render: rayschunk too large for windowed normalisation unless netchunk % P == 0");
+  if (a->shard_row_rays > 0) {
+    NR_REQUIRE(a->normal_mode == 1 && a->window_ss && a->window_reduce, NR_ERR_ARG,
+               "nr_unisurf_render: a sharded render needs normal_mode 1, window_ss and window_reduce");
+    const int64_t nloc = a->rays_per_batch > 0 ? a->rays_per_batch : a->n_rays;
+    NR_REQUIRE(a->shard_ray0 >= 0 && a->shard_ray0 + nloc <= a->shard_row_rays, NR_ERR_ARG,
+               "nr_unisurf_render: shard outside its batch row");
+  }
+  return NR_OK;
+}
+
 }  // namespace nr
+
+using namespace nr;
+
+extern "C" size_t nr_unisurf_workspace_bytes(const NrUnisurfArgs* a) {
+  if (!a || check_unisurf(a)) return 0;
+  UniChunk c;
+  UniHost h;
+  return unisurf_bind(*a, unisurf_chunk_rays(*a), nullptr, c, h);
+}
+
+extern "C" int64_t nr_unisurf_window_count(const NrUnisurfArgs* a) {
+  if (!a || a->normal_mode != 1) return 0;
+  int64_t rc_rays, nw_full, nw_row;
+  unisurf_windows(*a, rc_rays, nw_full, nw_row);
+  return nw_row;
+}
+
+extern "C" int nr_unisurf_render(const NrUnisurfArgs* a, void* stream) {
+  int rc = check_unisurf(a);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool sharded = a->shard_row_rays > 0;
+  if (a->n_rays <= 0) {  // an empty shard still joins the collective
+    if (sharded) NR_REQUIRE(a->window_reduce(a->window_user) == 0, NR_ERR_ARG, "nr_unisurf_render: window_reduce failed");
+    return NR_OK;
+  }
+  const int64_t Rc = unisurf_chunk_rays(*a);
+  UniChunk c;
+  UniHost h;
+  const size_t total = unisurf_bind(*a, Rc, (char*)a->workspace, c, h);
+  NR_REQUIRE(a->workspace && a->workspace_bytes >= total, NR_ERR_WORKSPACE, "nr_unisurf_render: workspace too small");
+  if (sharded)  // the whole shard (every batch row) is one chunk: one window reduction per call
+    return unisurf_chunk(*a, c, h, 0, (int)a->n_rays, a->shard_ray0,
+                         (int)(a->rays_per_batch > 0 ? a->rays_per_batch : a->n_rays), st);
+  const int64_t per_b = (a->normal_mode == 1 && a->rays_per_batch > 0) ? a->rays_per_batch : a->n_rays;
+  // window mode: chunks restart at every batch row and at every reference ray chunk
+  const int64_t span = a->normal_mode == 1 ? (a->rayschunk < per_b ? a->rayschunk : per_b) : per_b;
+  for (int64_t b0 = 0; b0 < a->n_rays; b0 += per_b)
+    for (int64_t c0 = b0; c0 < std::min(b0 + per_b, a->n_rays); c0 += span) {
+      const int64_t c1 = std::min(c0 + span, std::min(b0 + per_b, a->n_rays));
+      if ((rc = for_chunks(c1 - c0, Rc, [&](int64_t r0, int R) {
+             return unisurf_chunk(*a, c, h, c0 + r0, R, c0 + r0 - b0, R, st);
+           })))
+        return rc;
+    }
+  return NR_OK;
+}

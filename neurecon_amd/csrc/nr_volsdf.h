@@ -53,16 +53,11 @@ struct VolOut {
   float* sigma_bg; float* radiance_bg;
 };
 
-struct VolPlan {
-  int64_t Rc;
-  size_t o_ro, o_rd, o_Ld0, o_Ld1, o_Ls0, o_Ls1, o_dn0, o_dn1, o_pts, o_sraw, o_act0, o_act1, o_cnt;
-  size_t o_beta, o_fine, o_usage, o_bmap, o_dall, o_ptsf, o_sdff, o_nabf, o_featf, o_radf, o_mlp;
-  size_t o_farr, o_bp0, o_dout, o_x4, o_sigo, o_rado;
-  size_t total;
-  size_t lds_bytes;  // dynamic LDS of the per-ray kernels
+// what only the host orchestration reads (nr_volsdf.hip volsdf_bind / volsdf_chunk)
+struct VolHost {
+  void* mlp_ws; size_t mlp_bytes;  // the MLP kernels' reverse-pass scratch: the rest of the workspace
+  size_t lds_bytes;                // dynamic LDS of the per-ray kernels
 };
-
-VolPlan volsdf_plan(const NrVolsdfArgs& a, int64_t Rc);
 
 __global__ void volsdf_prologue(VolChunk c, const float* rays_o, const float* rays_d);
 __global__ void volsdf_first(VolChunk c);

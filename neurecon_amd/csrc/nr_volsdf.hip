@@ -8,8 +8,12 @@
 // (accumulate in double, round each prefix to float).  Only rays that are still refining stay
 // in the active list, and the SDF MLP launches read the active count from device memory, so no
 // host synchronisation is needed between rounds.
+#include <algorithm>
+#include <cstdint>
+
 #include "nr_common.h"
 #include "nr_mlp.h"
+#include "nr_render.h"
 #include "nr_volsdf.h"
 
 namespace nr {
@@ -616,55 +620,188 @@ __global__ __launch_bounds__(64) void volsdf_composite(VolChunk c, VolOut o, int
 }
 
 // ---------------------------------------------------------------------------------------------
-// workspace plan
+// host orchestration: workspace binding, one ray chunk, argument checks, entry points
 // ---------------------------------------------------------------------------------------------
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+// Fills the chunk view `c` (sampler constants, workspace pointers) and the host-only items `h` for chunks
+// of up to Rc rays carved from `base`; returns the workspace bytes.  base == nullptr sizes only.
+static size_t volsdf_bind(const NrVolsdfArgs& a, int64_t Rc, char* base, VolChunk& c, VolHost& h) {
+  c = VolChunk{};
+  c.N0 = 4 * a.N_samples;
+  c.N_up = 4 * a.N_samples;
+  c.cap = c.N0 + a.max_upsample_steps * c.N_up;
+  c.N_samples = a.N_samples;
+  c.N_imp = a.N_importance;
+  c.S = a.N_samples + a.N_importance;
+  c.max_iter = a.max_upsample_steps;
+  c.max_bisect = a.max_bisection_steps;
+  c.alpha_net = a.alpha_net;
+  c.beta_net = a.beta_net;
+  c.beta_plus0 = a.beta_plus_init;
+  c.eps = a.eps;
+  c.near = a.near;
+  c.far = a.far;
+  c.r_bg = a.obj_bounding_radius;
+  c.use_bg = a.use_sphere_bg;
+  c.t_coarse = a.t_coarse; c.t_init = a.t_init; c.u_up = a.u_up; c.u_fine = a.u_fine;
+  c.N_out = a.N_outside > 0 ? a.N_outside : 0;
+  c.beta_k = a.beta_plus_k;
+  c.rs_out = a.rs_out;
+  const size_t cap = c.cap, S = c.S, No = c.N_out, nq = std::max(c.N0, c.N_up);
+  Carve cv{base, 0};
+  c.ro = cv.take(Rc * 3);
+  c.rd = cv.take(Rc * 3);
+  c.Ld[0] = cv.take(Rc * cap);
+  c.Ld[1] = cv.take(Rc * cap);
+  c.Ls[0] = cv.take(Rc * cap);
+  c.Ls[1] = cv.take(Rc * cap);
+  c.dnew[0] = cv.take((size_t)Rc * c.N_up);
+  c.dnew[1] = cv.take((size_t)Rc * c.N_up);
+  c.pts = cv.take(Rc * nq * 3);
+  c.sraw = cv.take(Rc * nq);
+  c.act[0] = cv.take<int>(Rc);
+  c.act[1] = cv.take<int>(Rc);
+  c.cnt = cv.take<int>(a.max_upsample_steps + 1);
+  c.beta = cv.take(Rc);
+  c.fine = cv.take((size_t)Rc * a.N_importance);
+  c.usage = cv.take(Rc);
+  c.bmap = cv.take(Rc);
+  c.d_all = cv.take(Rc * S);
+  c.pts_f = cv.take(Rc * S * 3);
+  c.sdf_f = cv.take(Rc * S);
+  c.nab_f = cv.take(Rc * S * 3);
+  c.feat_f = cv.take(Rc * S * 256);
+  c.rad_f = cv.take(Rc * S * 3);
+  c.farr = cv.take(Rc);
+  c.bp0 = cv.take(Rc);
+  c.d_out = cv.take(Rc * No + 1);
+  c.x4 = cv.take(Rc * No * 4 + 1);
+  c.sig_o = cv.take(Rc * No + 1);
+  c.rad_o = cv.take(Rc * No * 3 + 1);
+  h.mlp_ws = base ? base + cv.off : nullptr;
+  h.mlp_bytes = base ? a.workspace_bytes - cv.off : 0;
+  const int big = std::max(c.cap, c.S + c.N_out), small = std::max(c.N_up, a.N_importance);
+  h.lds_bytes = (size_t)(2 * big + 2 * small + 4) * 4;  // dynamic LDS of the per-ray kernels
+  return cv.off + nr_mlp_workspace_bytes(1);
+}
 
-VolPlan volsdf_plan(const NrVolsdfArgs& a, int64_t Rc) {
-  VolPlan p{};
-  const int N0 = 4 * a.N_samples, N_up = 4 * a.N_samples;
-  const int cap = N0 + a.max_upsample_steps * N_up;
-  const int S = a.N_samples + a.N_importance;
-  const int nq = N0 > N_up ? N0 : N_up;
-  p.Rc = Rc;
-  size_t off = 0;
-  auto take = [&](size_t words) { size_t o = off; off = align_up(off + words * 4); return o; };
-  p.o_ro = take(Rc * 3);
-  p.o_rd = take(Rc * 3);
-  p.o_Ld0 = take((size_t)Rc * cap);
-  p.o_Ld1 = take((size_t)Rc * cap);
-  p.o_Ls0 = take((size_t)Rc * cap);
-  p.o_Ls1 = take((size_t)Rc * cap);
-  p.o_dn0 = take((size_t)Rc * N_up);
-  p.o_dn1 = take((size_t)Rc * N_up);
-  p.o_pts = take((size_t)Rc * nq * 3);
-  p.o_sraw = take((size_t)Rc * nq);
-  p.o_act0 = take(Rc);
-  p.o_act1 = take(Rc);
-  p.o_cnt = take(a.max_upsample_steps + 1);
-  p.o_beta = take(Rc);
-  p.o_fine = take((size_t)Rc * a.N_importance);
-  p.o_usage = take(Rc);
-  p.o_bmap = take(Rc);
-  p.o_dall = take((size_t)Rc * S);
-  p.o_ptsf = take((size_t)Rc * S * 3);
-  p.o_sdff = take((size_t)Rc * S);
-  p.o_nabf = take((size_t)Rc * S * 3);
-  p.o_featf = take((size_t)Rc * S * 256);
-  p.o_radf = take((size_t)Rc * S * 3);
-  const int No = a.N_outside > 0 ? a.N_outside : 0;
-  p.o_farr = take(Rc);
-  p.o_bp0 = take(Rc);
-  p.o_dout = take((size_t)Rc * No + 1);
-  p.o_x4 = take((size_t)Rc * No * 4 + 1);
-  p.o_sigo = take((size_t)Rc * No + 1);
-  p.o_rado = take((size_t)Rc * No * 3 + 1);
-  p.o_mlp = off;
-  p.total = off + nr_mlp_workspace_bytes(1);
-  const int big = cap > S + No ? cap : S + No;
-  const int small = N_up > a.N_importance ? N_up : a.N_importance;
-  p.lds_bytes = (size_t)(2 * big + 2 * small + 4) * 4;
-  return p;
+// One chunk (volsdf.py:394-551): prologue -> SDF(4 N_samples) -> first check -> [SDF(active x N_up,
+// device count) -> round it] x max_iter -> points -> SDF+nablas+feature -> radiance -> composite.
+// No host synchronisation inside a chunk.
+static int volsdf_chunk(const NrVolsdfArgs& a, VolChunk c, const VolHost& h, int64_t ray0, int R, hipStream_t st) {
+  c.R = R;
+  c.u_rand = a.u_rand ? a.u_rand + ray0 * a.N_importance : nullptr;
+  c.u_out = a.u_out && c.N_out > 0 ? a.u_out + ray0 * c.N_out : nullptr;
+  const SdfLayout SL = sdf_layout(*a.sdf);
+  const RadLayout RL = rad_layout(*a.rad);
+  const unsigned lds = (unsigned)h.lds_bytes;
+  const dim3 blk(64), grd((unsigned)R);
+  int rc;
+  NR_HIP_CHECK(hipMemsetAsync(c.cnt, 0, sizeof(int) * (a.max_upsample_steps + 1), st));
+  {
+    ProfScope prof("volsdf_prologue", (double)R, st);
+    hipLaunchKernelGGL(volsdf_prologue, grd, blk, 0, st, c, a.rays_o + ray0 * 3, a.rays_d + ray0 * 3);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  if ((rc = launch_sdf(SL, a.sdf_packed, c.pts, (int64_t)c.N0 * R, c.sraw, nullptr, nullptr, a.sdf->multires,
+                       nullptr, 0, st)))
+    return rc;
+  {
+    ProfScope prof("volsdf_first", (double)R, st);
+    hipLaunchKernelGGL(volsdf_first, grd, blk, lds, st, c);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  for (int it = 1; it <= a.max_upsample_steps; ++it) {
+    if ((rc = launch_sdf(SL, a.sdf_packed, c.pts, (int64_t)c.N_up * R, c.sraw, nullptr, nullptr, a.sdf->multires,
+                         nullptr, 0, st, c.cnt + (it - 1), c.N_up)))
+      return rc;
+    {
+      ProfScope prof("volsdf_iter", (double)R, st);
+      hipLaunchKernelGGL(volsdf_iter, grd, blk, lds, st, c, it);
+    }
+    NR_HIP_CHECK(hipGetLastError());
+  }
+  {
+    ProfScope prof("volsdf_points", (double)R, st);
+    hipLaunchKernelGGL(volsdf_points, grd, blk, lds, st, c);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  const int64_t P = (int64_t)c.S * R;
+  if ((rc = launch_sdf(SL, a.sdf_packed, c.pts_f, P, c.sdf_f, c.nab_f, c.feat_f, a.sdf->multires, h.mlp_ws,
+                       h.mlp_bytes, st)))
+    return rc;
+  if ((rc = launch_radiance(RL, a.rad_packed, c.pts_f, c.rd, c.S, INT64_MAX, c.nab_f, c.feat_f, P, c.rad_f,
+                            a.rad->multires_view, st)))
+    return rc;
+  if (c.N_out > 0) {
+    {
+      ProfScope prof("volsdf_outside", (double)R, st);
+      hipLaunchKernelGGL(volsdf_outside, grd, blk, 0, st, c);
+    }
+    NR_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_nerf(nerf_layout(*a.nerf), a.nerf_packed, c.x4, c.rd, c.N_out, INT64_MAX,
+                          (int64_t)c.N_out * R, c.sig_o, c.rad_o, st)))
+      return rc;
+  }
+  VolOut o{ray0, a.rgb, a.depth, a.acc, a.normals, a.d_vals, a.sdf_out, a.nablas_out, a.radiance_out,
+           a.alpha_out, a.p_out, a.weights_out, a.sigma_out, a.beta_map, a.iter_usage, a.sigma_bg, a.radiance_bg};
+  {
+    ProfScope prof("volsdf_composite", (double)R, st);
+    hipLaunchKernelGGL(volsdf_composite, grd, blk, lds, st, c, o, a.calc_normal, a.white_bkgd);
+  }
+  NR_HIP_CHECK(hipGetLastError());
+  return NR_OK;
+}
+
+static int64_t volsdf_chunk_rays(const NrVolsdfArgs* a) {
+  const int64_t cap = 16384;
+  return a->n_rays < cap ? (a->n_rays > 0 ? a->n_rays : 1) : cap;
+}
+
+static int check_volsdf(const NrVolsdfArgs* a) {
+  static const char* const kName = "nr_volsdf_render";
+  int rc = check_render_common(kName, a);
+  if (rc) return rc;
+  NR_REQUIRE(a->sdf_packed && a->rad_packed && a->t_coarse && a->t_init && a->u_up && a->u_fine, NR_ERR_ARG,
+             "nr_volsdf_render: null argument");
+  if ((rc = check_render_normals(kName, a))) return rc;
+  NR_REQUIRE(a->N_samples >= 1 && a->N_importance >= 1 && a->max_upsample_steps >= 0 && a->max_bisection_steps >= 0,
+             NR_ERR_ARG, "nr_volsdf_render: bad sample counts");
+  NR_REQUIRE(4 * a->N_samples <= 1024 && a->N_importance <= 1024, NR_ERR_UNSUPPORTED,
+             "nr_volsdf_render: 4*N_samples and N_importance must be <= 1024");
+  NR_REQUIRE(a->beta_net > 0.f && (a->N_outside > 0 || a->beta_plus_init > 0.f), NR_ERR_ARG,
+             "nr_volsdf_render: beta must be positive");
+  if (a->N_outside > 0) {
+    NR_REQUIRE(!a->use_sphere_bg, NR_ERR_ARG, "nr_volsdf_render: NeRF++ background excludes the builtin sphere");
+    NR_REQUIRE(a->nerf && a->nerf_packed && a->rs_out && a->beta_plus_k > 0.f, NR_ERR_ARG,
+               "nr_volsdf_render: N_outside > 0 needs nerf, nerf_packed, rs_out and beta_plus_k");
+    if ((rc = check_nerf_desc(a->nerf))) return rc;
+  }
+  return NR_OK;
 }
 
 }  // namespace nr
+
+using namespace nr;
+
+extern "C" size_t nr_volsdf_workspace_bytes(const NrVolsdfArgs* a) {
+  if (!a || check_volsdf(a)) return 0;
+  VolChunk c;
+  VolHost h;
+  return volsdf_bind(*a, volsdf_chunk_rays(a), nullptr, c, h);
+}
+
+extern "C" int nr_volsdf_render(const NrVolsdfArgs* a, void* stream) {
+  int rc = check_volsdf(a);
+  if (rc || a->n_rays <= 0) return rc;
+  const int64_t Rc = volsdf_chunk_rays(a);
+  VolChunk c;
+  VolHost h;
+  const size_t total = volsdf_bind(*a, Rc, (char*)a->workspace, c, h);
+  NR_REQUIRE(a->workspace && a->workspace_bytes >= total, NR_ERR_WORKSPACE, "nr_volsdf_render: workspace too small");
+  size_t lds_max;
+  if ((rc = lds_limit(lds_max))) return rc;
+  NR_REQUIRE(h.lds_bytes <= lds_max, NR_ERR_UNSUPPORTED,
+             "nr_volsdf_render: per-ray sample list does not fit in LDS (reduce N_samples or max_upsample_steps)");
+  return for_chunks(a->n_rays, Rc, [&](int64_t r0, int R) { return volsdf_chunk(*a, c, h, r0, R, (hipStream_t)stream); });
+}
+

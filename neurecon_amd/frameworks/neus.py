@@ -7,7 +7,6 @@ alpha compositing) runs in libnrhip.so (`nr_neus_render`).
 """
 import copy
 import ctypes
-import math
 from collections import OrderedDict
 
 import numpy as np
@@ -16,8 +15,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib as L
-from ..base import ImplicitSurface, NeRF, RadianceNet, _no_training, check_view_dirs, wants_graph
 from .. import rend_util
+from ..base import ImplicitSurface, NeRF, RadianceNet, check_view_dirs, wants_graph
+from . import _shell
+from ._shell import (HEAD, _linspace_table, alloc_outputs, bind_outputs, bypass, extras_of, f32, flat_rays, net_cfgs,
+                     normals_volume, run, train_points)
 
 
 class NeuS(nn.Module):
@@ -50,19 +52,6 @@ class NeuS(nn.Module):
         return radiances, sdf, nablas
 
 
-_TABLES = {}
-
-
-def _linspace_table(n, device):
-    """torch.linspace(0, 1, n) computed on the CPU exactly as the reference does, uploaded once."""
-    key = (n, str(device))
-    t = _TABLES.get(key)
-    if t is None:
-        t = torch.linspace(0, 1, n).float().to(device)
-        _TABLES[key] = t
-    return t
-
-
 def _neus_uniforms(B, N, batched, rayschunk, direct, n_iters, n_up, N_importance, N_outside, dev):
     """perturb=True uniforms in the reference's draw order (neus.py:385-397 ray-chunk loop; per chunk
     sample_pdf's torch.rand(..., device) per upsampling round (rend_util.py:271) and the NeRF++
@@ -85,6 +74,51 @@ def _neus_uniforms(B, N, batched, rayschunk, direct, n_iters, n_up, N_importance
         u = (u.reshape(B * N, N_importance) if direct else u.reshape(n_iters, B * N, n_up)).contiguous()
     t_out = torch.cat(outs, len(pre)).reshape(B * N, N_outside).contiguous() if outs else None
     return u, t_out
+
+
+# a render's outputs in the order of its extras (neus.py:345-380); S samples, M = S - 1 + N_outside
+OUTPUTS = HEAD + [
+    ('implicit_nablas', 'nablas_out', ('S', 3), f32, ('detailed',)),
+    ('implicit_surface', 'sdf_out', ('S',), f32, ('detailed',)),
+    ('radiance', 'radiance_out', ('M', 3), f32, ('detailed',)),
+    ('alpha', 'alpha_out', ('M',), f32, ('detailed',)),
+    ('cdf', 'cdf_out', ('S',), f32, ('detailed',)),
+    ('visibility_weights', 'weights_out', ('M',), f32, ('detailed',)),
+    ('d_final', 'd_final', ('M',), f32, ('detailed',)),
+    ('sigma_out', 'sigma_out', ('M',), f32, ('detailed', 'outside')),
+    ('radiance_out', 'radiance_bg_out', ('M', 3), f32, ('detailed', 'outside')),
+]
+
+
+def _counts(upsample_algo, N_samples, N_importance, N_upsample_iters):
+    """direct, new samples per sample_pdf (direct: one of N_importance, neus.py:215-243), total samples S"""
+    if upsample_algo not in L.UPSAMPLE:
+        raise NotImplementedError(upsample_algo)
+    direct = upsample_algo != 'official_solution'
+    n_up = N_importance if direct else (N_importance // N_upsample_iters if N_upsample_iters > 0 else 0)
+    return direct, n_up, N_samples + (N_importance if direct else N_upsample_iters * n_up)
+
+
+def _sampling_args(ro, rd, model, dev, rad_packed, obj_bounding_radius, rayschunk, max_workspace_gb, near_bypass,
+                   far_bypass, fixed_s_recp, N_samples, N_importance, upsample_algo, N_nograd_samples,
+                   N_upsample_iters, n_up):
+    """the argument fields that a render and the training's sample pass fill alike"""
+    sdf_desc, sdf_packed = model.implicit_surface.nr_packed(dev)
+    a = L.NrNeusArgs()
+    a.rays_o, a.rays_d, a.n_rays = L.ptr(ro), L.ptr(rd), ro.shape[0]
+    a.sdf, a.sdf_packed = ctypes.pointer(sdf_desc), L.ptr(sdf_packed)
+    a.rad, a.rad_packed = ctypes.pointer(model.radiance_net.nr_desc()), L.ptr(rad_packed)
+    a.obj_bounding_radius = float(obj_bounding_radius)
+    a.near_bypass, a.far_bypass = bypass(near_bypass), bypass(far_bypass)
+    a.N_samples, a.N_importance, a.N_upsample_iters = N_samples, N_importance, N_upsample_iters
+    a.t_coarse, a.u_fine = L.ptr(_linspace_table(N_samples, dev)), L.ptr(_linspace_table(max(n_up, 1), dev))
+    a.upsample_algo = L.UPSAMPLE[upsample_algo]
+    a.fixed_s = 1. / fixed_s_recp
+    if upsample_algo == 'direct_more':
+        a.N_nograd_samples, a.t_nograd = N_nograd_samples, L.ptr(_linspace_table(N_nograd_samples, dev))
+    a.max_chunk_rays = int(rayschunk) if rayschunk else 0
+    a.max_workspace_bytes = L.workspace_budget_bytes(max_workspace_gb)
+    return a
 
 
 def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False, batched_info={},
@@ -122,110 +156,38 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
                              N_samples=N_samples, N_importance=N_importance, N_outside=N_outside,
                              upsample_algo=upsample_algo, N_nograd_samples=N_nograd_samples,
                              N_upsample_iters=N_upsample_iters)
-    if upsample_algo not in L.UPSAMPLE:
-        raise NotImplementedError(upsample_algo)
-    direct = upsample_algo != 'official_solution'
+    direct, n_up, S = _counts(upsample_algo, N_samples, N_importance, N_upsample_iters)
     check_view_dirs(model, use_view_dirs)
     dev = rays_o.device
-    if batched:
-        B = rays_d.shape[0]
-        prefix = [B, -1]
-    else:
-        prefix = [-1]
-    ro = rays_o.reshape(-1, 3).float().contiguous()
-    rd = rays_d.reshape(-1, 3).float().contiguous()
-    n = ro.shape[0]
-    if direct:  # one sample_pdf of N_importance (neus.py:215-243)
-        n_up = N_importance
-        S = N_samples + N_importance
-    else:
-        n_up = N_importance // N_upsample_iters if N_upsample_iters > 0 else 0
-        S = N_samples + N_upsample_iters * n_up
-    M = S - 1 + N_outside  # samples after the NeRF++ merge (neus.py:325-343)
-
-    sdf_desc, sdf_packed = model.implicit_surface.nr_packed(dev)
-    rad_desc, rad_packed = model.radiance_net.nr_packed(dev)
+    ro, rd, n, B, prefix = flat_rays(rays_o, rays_d, batched)
+    flags = dict(calc_normal=calc_normal, detailed=detailed_output, outside=N_outside > 0)
+    rad_packed = model.radiance_net.nr_packed(dev)[1]
     s_dev = model.forward_s().detach().float().reshape(-1)[:1].contiguous()  # stays on the device
-    t_coarse = _linspace_table(N_samples, dev)
-    u_fine = _linspace_table(max(n_up, 1), dev)
-
-    rgb = torch.empty(n, 3, device=dev)
-    depth = torch.empty(n, device=dev)
-    acc = torch.empty(n, device=dev)
-    normals = torch.empty(n, 3, device=dev) if calc_normal else None
-    det = {}
-    if detailed_output:
-        det = dict(implicit_nablas=torch.empty(n, S, 3, device=dev), implicit_surface=torch.empty(n, S, device=dev),
-                   radiance=torch.empty(n, M, 3, device=dev), alpha=torch.empty(n, M, device=dev),
-                   cdf=torch.empty(n, S, device=dev), visibility_weights=torch.empty(n, M, device=dev),
-                   d_final=torch.empty(n, M, device=dev))
-        if N_outside > 0:
-            det['sigma_out'] = torch.empty(n, M, device=dev)
-            det['radiance_out'] = torch.empty(n, M, 3, device=dev)
-    a = L.NrNeusArgs()
-    a.rays_o, a.rays_d, a.n_rays = L.ptr(ro), L.ptr(rd), n
-    a.sdf, a.sdf_packed = ctypes.pointer(sdf_desc), L.ptr(sdf_packed)
-    a.rad, a.rad_packed = ctypes.pointer(rad_desc), L.ptr(rad_packed)
+    a = _sampling_args(ro, rd, model, dev, rad_packed, obj_bounding_radius, rayschunk, max_workspace_gb, near_bypass,
+                       far_bypass, fixed_s_recp, N_samples, N_importance, upsample_algo, N_nograd_samples,
+                       N_upsample_iters, n_up)
+    # M = samples after the NeRF++ merge (neus.py:325-343)
+    out = alloc_outputs(OUTPUTS, n, dict(S=S, M=S - 1 + N_outside), flags, dev)
+    bind_outputs(OUTPUTS, a, out)
     fold_packed = model.radiance_net.nr_fold_packed(model.implicit_surface, dev) if fold_feature else None
     a.fold_packed = L.ptr(fold_packed)
     a.s, a.s_dev = 0.0, L.ptr(s_dev)
     a.no_mid_skip = 0 if skip_zero_alpha else 1
     a.no_defer = 0 if defer_sample_nablas else 1
-    a.max_chunk_rays = int(rayschunk) if rayschunk else 0
-    a.max_workspace_bytes = L.workspace_budget_bytes(max_workspace_gb)
-    a.obj_bounding_radius = float(obj_bounding_radius)
-    a.near_bypass = float('nan') if near_bypass is None else float(near_bypass)
-    a.far_bypass = float('nan') if far_bypass is None else float(far_bypass)
-    a.N_samples, a.N_importance, a.N_upsample_iters = N_samples, N_importance, N_upsample_iters
     a.calc_normal, a.white_bkgd = int(bool(calc_normal)), int(bool(white_bkgd))
-    a.t_coarse, a.u_fine = L.ptr(t_coarse), L.ptr(u_fine)
-    a.upsample_algo = L.UPSAMPLE[upsample_algo]
-    a.fixed_s = 1. / fixed_s_recp
-    if upsample_algo == 'direct_more':
-        t_nograd = _linspace_table(N_nograd_samples, dev)
-        a.N_nograd_samples, a.t_nograd = N_nograd_samples, L.ptr(t_nograd)
-    a.rgb, a.depth, a.acc, a.normals = L.ptr(rgb), L.ptr(depth), L.ptr(acc), L.ptr(normals)
-    a.d_final = L.ptr(det.get('d_final'))
-    a.sdf_out = L.ptr(det.get('implicit_surface'))
-    a.nablas_out = L.ptr(det.get('implicit_nablas'))
-    a.radiance_out = L.ptr(det.get('radiance'))
-    a.alpha_out = L.ptr(det.get('alpha'))
-    a.cdf_out = L.ptr(det.get('cdf'))
-    a.weights_out = L.ptr(det.get('visibility_weights'))
     if N_outside > 0:
         if not hasattr(model, 'nerf_outside'):
             raise ValueError('N_outside > 0 needs a model built with use_outside_nerf=True')
         nerf_desc, nerf_packed = model.nerf_outside.nr_packed(dev)
-        t_out = _linspace_table(N_outside + 2, dev)
         a.nerf, a.nerf_packed = ctypes.pointer(nerf_desc), L.ptr(nerf_packed)
-        a.N_outside, a.t_outside = N_outside, L.ptr(t_out)
-        a.sigma_out, a.radiance_bg_out = L.ptr(det.get('sigma_out')), L.ptr(det.get('radiance_out'))
+        a.N_outside, a.t_outside = N_outside, L.ptr(_linspace_table(N_outside + 2, dev))
     if perturb:
-        B = rays_d.shape[0] if batched else 1
         u_rand, t_out_rand = _neus_uniforms(B, n // B, batched, int(rayschunk), direct, N_upsample_iters, n_up,
                                             N_importance, N_outside, dev)
         a.u_rand, a.t_out_rand = L.ptr(u_rand), L.ptr(t_out_rand)
     lib = L.lib()
-    ws_bytes = lib.nr_neus_workspace_bytes(ctypes.byref(a))
-    ws = L.workspace(dev, ws_bytes)
-    a.workspace, a.workspace_bytes = L.ptr(ws), ws_bytes
-    L.check(lib.nr_neus_render(ctypes.byref(a), L.stream_of(dev)))
-
-    ret = OrderedDict([('rgb', rgb.reshape(*prefix, 3)), ('depth_volume', depth.reshape(prefix)),
-                       ('mask_volume', acc.reshape(prefix))])
-    if calc_normal:
-        ret['normals_volume'] = normals.reshape(*prefix, 3)
-    if detailed_output:
-        ret['implicit_nablas'] = det['implicit_nablas'].reshape(*prefix, S, 3)
-        ret['implicit_surface'] = det['implicit_surface'].reshape(*prefix, S)
-        ret['radiance'] = det['radiance'].reshape(*prefix, M, 3)
-        ret['alpha'] = det['alpha'].reshape(*prefix, M)
-        ret['cdf'] = det['cdf'].reshape(*prefix, S)
-        ret['visibility_weights'] = det['visibility_weights'].reshape(*prefix, M)
-        ret['d_final'] = det['d_final'].reshape(*prefix, M)
-        if N_outside > 0:
-            ret['sigma_out'] = det['sigma_out'].reshape(*prefix, M)
-            ret['radiance_out'] = det['radiance_out'].reshape(*prefix, M, 3)
+    run(lib.nr_neus_workspace_bytes, lib.nr_neus_render, a, dev)
+    ret = extras_of(OUTPUTS, out, prefix, flags)
     return ret['rgb'], ret['depth_volume'], ret
 
 
@@ -235,42 +197,20 @@ def _sample_depths(ro, rd, model, dev, obj_bounding_radius, batched, B, rayschun
     """The no-grad upsampling of a training step (neus.py:206-279): sorted sample depths [n, S] from
     the render kernels' sample pass (forward-only SDF launches, no compositing), and with perturb the
     NeRF++ strata uniforms [n, N_outside] (or None)."""
-    direct = upsample_algo != 'official_solution'
+    direct, n_up, S = _counts(upsample_algo, N_samples, N_importance, N_upsample_iters)
     n = ro.shape[0]
-    n_up = N_importance if direct else (N_importance // N_upsample_iters if N_upsample_iters > 0 else 0)
-    S = N_samples + (N_importance if direct else N_upsample_iters * n_up)
-    sdf_desc, sdf_packed = model.implicit_surface.nr_packed(dev)
-    rad_desc = model.radiance_net.nr_desc()  # the sample pass never evaluates the radiance net: no pack
+    # the sample pass never evaluates the radiance net: no pack
+    a = _sampling_args(ro, rd, model, dev, None, obj_bounding_radius, rayschunk, None, near_bypass, far_bypass,
+                       fixed_s_recp, N_samples, N_importance, upsample_algo, N_nograd_samples, N_upsample_iters, n_up)
     d_all = torch.empty(n, S, device=dev)
-    a = L.NrNeusArgs()
-    a.rays_o, a.rays_d, a.n_rays = L.ptr(ro), L.ptr(rd), n
-    a.sdf, a.sdf_packed = ctypes.pointer(sdf_desc), L.ptr(sdf_packed)
-    a.rad, a.rad_packed = ctypes.pointer(rad_desc), None
-    a.obj_bounding_radius = float(obj_bounding_radius)
-    a.near_bypass = float('nan') if near_bypass is None else float(near_bypass)
-    a.far_bypass = float('nan') if far_bypass is None else float(far_bypass)
-    a.N_samples, a.N_importance, a.N_upsample_iters = N_samples, N_importance, N_upsample_iters
-    t_coarse = _linspace_table(N_samples, dev)
-    u_fine = _linspace_table(max(n_up, 1), dev)
-    a.t_coarse, a.u_fine = L.ptr(t_coarse), L.ptr(u_fine)
-    a.upsample_algo = L.UPSAMPLE[upsample_algo]
-    a.fixed_s = 1. / fixed_s_recp
-    if upsample_algo == 'direct_more':
-        t_nograd = _linspace_table(N_nograd_samples, dev)
-        a.N_nograd_samples, a.t_nograd = N_nograd_samples, L.ptr(t_nograd)
     t_out = None
     if perturb:  # the NeRF++ strata uniforms are drawn in the same per-chunk order as the render's
         u_rand, t_out = _neus_uniforms(B, n // B, batched, int(rayschunk), direct, N_upsample_iters, n_up,
                                        N_importance, N_outside, dev)
         a.u_rand = L.ptr(u_rand)
     a.sample_only, a.d_all_out = 1, L.ptr(d_all)
-    a.max_chunk_rays = int(rayschunk) if rayschunk else 0
-    a.max_workspace_bytes = L.workspace_budget_bytes()
     lib = L.lib()
-    ws_bytes = lib.nr_neus_workspace_bytes(ctypes.byref(a))
-    ws = L.workspace(dev, ws_bytes)
-    a.workspace, a.workspace_bytes = L.ptr(ws), ws_bytes
-    L.check(lib.nr_neus_render(ctypes.byref(a), L.stream_of(dev)))
+    run(lib.nr_neus_workspace_bytes, lib.nr_neus_render, a, dev)
     return d_all, t_out
 
 
@@ -301,26 +241,14 @@ def _train_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
     implicit_surface, radiance, visibility_weights."""
     from .. import training as T
     check_view_dirs(model, use_view_dirs)
-    if upsample_algo not in L.UPSAMPLE:
-        raise NotImplementedError(upsample_algo)
     dev = rays_o.device
-    B = rays_d.shape[0] if batched else 1
-    prefix = [B, -1] if batched else [-1]
-    ro = rays_o.reshape(-1, 3).float().contiguous()
-    rd_raw = rays_d.reshape(-1, 3).float().contiguous()
-    n = ro.shape[0]
-    rd = torch.empty_like(rd_raw)  # F.normalize(rays_d, dim=-1) (neus.py:172)
-    L.check(L.lib().nr_normalize3(L.ptr(rd_raw), n, L.ptr(rd), L.stream_of(dev)))
+    ro, rd_raw, n, B, prefix = flat_rays(rays_o, rays_d, batched)
     with torch.no_grad():
         d_all, t_out = _sample_depths(ro, rd_raw, model, dev, obj_bounding_radius, batched, B, rayschunk, near_bypass,
                                       far_bypass, perturb, fixed_s_recp, N_samples, N_importance, upsample_algo,
                                       N_nograd_samples, N_upsample_iters, N_outside)
     S = d_all.shape[1]
-    pts = torch.empty(n, S, 3, device=dev)
-    mids = torch.empty(n, S - 1, 3, device=dev)
-    dmid = torch.empty(n, S - 1, device=dev)
-    L.check(L.lib().nr_neus_points(L.ptr(ro), L.ptr(rd), L.ptr(d_all), n, S, L.ptr(pts), L.ptr(mids), L.ptr(dmid),
-                                   L.stream_of(dev)))
+    rd, pts, mids, dmid = train_points(ro, rd_raw, d_all)  # F.normalize(rays_d, dim=-1) (neus.py:172)
     surf = model.implicit_surface
     Ws = T.effective_weights(surf)  # one weight_norm per layer, shared by both evaluations
     if T.uses_train_gemm(surf):  # samples and mid-points in one evaluation (feature for the mid-points only)
@@ -334,6 +262,7 @@ def _train_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
     view = rd[:, None, :].expand(n, S - 1, 3).reshape(-1, 3).contiguous()
     rad = T.radiance(model.radiance_net, mids.reshape(-1, 3), view, nab_m, feat_m)
     s = model.forward_s().float().reshape(-1)[:1]
+    out = {}
     if N_outside > 0:  # neus.py:303-343: the background net at cat([d_mid, outside depths])
         with torch.no_grad():
             d_out = torch.cat([dmid, _outside_depths(ro, rd, obj_bounding_radius, far_bypass, N_outside, t_out)], -1)
@@ -349,69 +278,40 @@ def _train_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
         rgb, depth, acc, w, alpha, cdf = T.NeuSCompositeBG.apply(sdf.reshape(n, S), s, rad.reshape(n, S - 1, 3),
                                                                  sig_o.reshape(n, M), rad_o.reshape(n, M, 3), d_out,
                                                                  inside, bool(white_bkgd))
-        d_final = d_out
+        out.update(d_final=d_out, sigma_out=sig_o.reshape(n, M), radiance_out=rad_o.reshape(n, M, 3))
     else:
         rgb, depth, acc, w, alpha, cdf = T.NeuSComposite.apply(sdf.reshape(n, S), s, rad.reshape(n, S - 1, 3), dmid,
                                                               bool(white_bkgd))
-        d_final = dmid
-    Mw = w.shape[1]
+        out.update(d_final=dmid)
     nablas = nablas.reshape(n, S, 3)
-    ret = OrderedDict([('rgb', rgb.reshape(*prefix, 3)), ('depth_volume', depth.reshape(prefix)),
-                       ('mask_volume', acc.reshape(prefix))])
+    # radiance: the surface net's colours at the mid-points
+    out.update(rgb=rgb, depth_volume=depth, mask_volume=acc, implicit_nablas=nablas, implicit_surface=sdf.reshape(n, S),
+               radiance=rad.reshape(n, S - 1, 3), alpha=alpha, cdf=cdf, visibility_weights=w)
     if calc_normal:  # neus.py:364-368
-        nrm = F.normalize(nablas, dim=-1)
-        k = min(w.shape[-1], nrm.shape[-2])
-        ret['normals_volume'] = (nrm[:, :k, :] * w[:, :k, None]).sum(dim=-2).reshape(*prefix, 3)
-    if detailed_output:
-        ret['implicit_nablas'] = nablas.reshape(*prefix, S, 3)
-        ret['implicit_surface'] = sdf.reshape(*prefix, S)
-        ret['radiance'] = rad.reshape(*prefix, S - 1, 3)  # the surface net's colours at the mid-points
-        ret['alpha'] = alpha.reshape(*prefix, Mw)
-        ret['cdf'] = cdf.reshape(*prefix, S)
-        ret['visibility_weights'] = w.reshape(*prefix, Mw)
-        ret['d_final'] = d_final.reshape(*prefix, Mw)
-        if N_outside > 0:
-            ret['sigma_out'] = sig_o.reshape(*prefix, Mw)
-            ret['radiance_out'] = rad_o.reshape(*prefix, Mw, 3)
+        out['normals_volume'] = normals_volume(nablas, w)
+    ret = extras_of(OUTPUTS, out, prefix, dict(calc_normal=calc_normal, detailed=detailed_output,
+                                               outside=N_outside > 0))
     return ret['rgb'], ret['depth_volume'], ret
 
 
-class SingleRenderer(nn.Module):
-    """neus.py:399-405 -- an nn.Module so nn.DataParallel can scatter rays over dim 1."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.model = model
-
-    def forward(self, rays_o, rays_d, **kwargs):
-        return volume_render(rays_o, rays_d, self.model, **kwargs)
+class SingleRenderer(_shell.SingleRenderer):
+    """neus.py:399-405"""
+    render = staticmethod(volume_render)
 
 
-class Trainer(nn.Module):
+class Trainer(_shell.Trainer):
     """neus.py:408-485: one training step's forward -- random rays of the image, the render with a
     graph (training autograd functions on libnrhip.so), L1 rgb + eikonal + BCE mask losses.  Returns
     OrderedDict(losses=..., extras=...) exactly like the reference; train.py calls backward() on
     losses['total'] (under DDP the gradient all-reduce runs over RCCL)."""
-
-    def __init__(self, model, device_ids=[0], batched=True):
-        super().__init__()
-        self.model = model
-        self.renderer = SingleRenderer(model)
-        if len(device_ids) > 1:
-            self.renderer = nn.DataParallel(self.renderer, device_ids=device_ids, dim=1 if batched else 0)
-        self.device = device_ids[0]
+    Renderer = SingleRenderer
 
     def forward(self, args, indices, model_input, ground_truth, render_kwargs_train, it, device='cuda'):
         from ..config import as_cfg
         args = as_cfg(args)
-        intrinsics = model_input['intrinsics'].to(device)
-        c2w = model_input['c2w'].to(device)
-        H, W = render_kwargs_train['H'], render_kwargs_train['W']
-        rays_o, rays_d, select_inds = rend_util.get_rays(c2w, intrinsics, H, W, N_rays=args.data.N_rays)
-        # [B, N_rays, 3] (neus.py:432)
-        target_rgb = rend_util.gather_rays(ground_truth['rgb'].to(device), select_inds)
-        mask_ignore = rend_util.gather_rays(model_input['mask_ignore'].to(device), select_inds) \
-            if 'mask_ignore' in model_input else None
+        # rays [B, N_rays, 3] (neus.py:432)
+        rays_o, rays_d, select_inds, target_rgb, mask_ignore = self.rays_and_targets(
+            args, model_input, ground_truth, render_kwargs_train, device)
         rgb, depth_v, extras = self.renderer(rays_o, rays_d, detailed_output=True, **render_kwargs_train)
         nablas = extras['implicit_nablas']
         nablas_norm = torch.norm(nablas, dim=-1)
@@ -433,10 +333,7 @@ class Trainer(nn.Module):
             losses['loss_img'] = (losses['loss_img'] * mask_ignore[..., None].float()).sum() / (mask_ignore.sum() + 1e-10)
         else:
             losses['loss_img'] = losses['loss_img'].mean()
-        loss = 0
-        for k, v in losses.items():
-            loss += losses[k]
-        losses['total'] = loss
+        self.sum_losses(losses)
         extras['implicit_nablas_norm'] = nablas_norm
         extras['scalars'] = {'1/s': 1. / self.model.forward_s().data}
         extras['select_inds'] = select_inds
@@ -457,26 +354,7 @@ def get_model(args):
         'speed_factor': args.training.setdefault('speed_factor', 1.0),
         'variance_init': args.model.setdefault('variance_init', 0.05),
     }
-    surface_cfg = {
-        'use_siren': args.model.surface.setdefault('use_siren', args.model.setdefault('use_siren', False)),
-        'embed_multires': args.model.surface.setdefault('embed_multires', 6),
-        'radius_init': args.model.surface.setdefault('radius_init', 1.0),
-        'geometric_init': args.model.surface.setdefault('geometric_init', True),
-        'D': args.model.surface.setdefault('D', 8),
-        'W': args.model.surface.setdefault('W', 256),
-        'skips': args.model.surface.setdefault('skips', [4]),
-    }
-    radiance_cfg = {
-        'use_siren': args.model.radiance.setdefault('use_siren', args.model.setdefault('use_siren', False)),
-        'embed_multires': args.model.radiance.setdefault('embed_multires', -1),
-        'embed_multires_view': args.model.radiance.setdefault('embed_multires_view', -1),
-        'use_view_dirs': args.model.radiance.setdefault('use_view_dirs', True),
-        'D': args.model.radiance.setdefault('D', 4),
-        'W': args.model.radiance.setdefault('W', 256),
-        'skips': args.model.radiance.setdefault('skips', []),
-    }
-    model_config['surface_cfg'] = surface_cfg
-    model_config['radiance_cfg'] = radiance_cfg
+    model_config['surface_cfg'], model_config['radiance_cfg'] = net_cfgs(args)
     model = NeuS(**model_config)
     render_kwargs_train = {
         'upsample_algo': args.model.setdefault('upsample_algo', 'official_solution'),

@@ -18,7 +18,9 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import rend_util
 from ..base import ImplicitSurface, RadianceNet, check_view_dirs, wants_graph
-from .neus import _linspace_table
+from . import _shell
+from ._shell import (HEAD, _linspace_table, alloc_outputs, bind_outputs, bypass, extras_of, f32, flat_rays, net_cfgs,
+                     normals_volume, run, train_points)
 
 N_STEPS = 256        # ray_casting.py:49 (root_finding_surface_points default)
 N_SECANT_STEPS = 8   # ray_casting.py:52
@@ -86,6 +88,23 @@ def _window_reducer(window_ss, group=None):
     return L.WINDOW_REDUCE(cb)
 
 
+# a render's outputs in the order of its extras (unisurf.py:255-281); P samples per ray.  d_all: the
+# sample depths, which only the training render returns
+OUTPUTS = HEAD + [
+    ('surface_points', 'surface_points', (3,), f32, ('detailed',)),
+    ('mask_surface', 'mask_surface', (), torch.bool, ('detailed',)),
+    ('depth_surface', 'depth_surface', (), f32, ('detailed',)),
+    ('radiance', 'radiance_out', ('P', 3), f32, ('detailed',)),
+    ('implicit_surface', 'sdf_out', ('P',), f32, ('detailed',)),
+    ('implicit_nablas', 'nablas_out', ('P', 3), f32, ('detailed',)),
+    ('alpha', 'alpha_out', ('P',), f32, ('detailed',)),
+    ('visibility_weights', 'weights_out', ('P',), f32, ('detailed',)),
+    ('d_all', 'd_all_out', ('P',), f32, ('detailed', 'd_all')),
+]
+# training's no-grad pass: sample depths + surface points only
+SAMPLE_OUTPUTS = [row for row in OUTPUTS if row[0] in ('surface_points', 'mask_surface', 'depth_surface', 'd_all')]
+
+
 def volume_render(rays_o, rays_d, model, batched=False, batched_info={}, calc_normal=False, logit_tau=0.0,
                   use_view_dirs=True, method='secant', rayschunk=65536, netchunk=1048576, white_bkgd=False,
                   near_bypass=None, far_bypass=None, detailed_output=True, show_progress=False,
@@ -110,48 +129,20 @@ def volume_render(rays_o, rays_d, model, batched=False, batched_info={}, calc_no
                              N_freespace=N_freespace)
     check_view_dirs(model, use_view_dirs)
     dev = rays_o.device
-    if batched:
-        B, N = rays_d.shape[0], rays_d.reshape(rays_d.shape[0], -1, 3).shape[1]
-        prefix = [B, -1]
-    else:
-        N = rays_d.reshape(-1, 3).shape[0]
-        prefix = [-1]
-    ro = rays_o.reshape(-1, 3).float().contiguous()
-    rd = rays_d.reshape(-1, 3).float().contiguous()
-    n = ro.shape[0]
-    P = N_query + N_freespace
+    ro, rd, n, B, prefix = flat_rays(rays_o, rays_d, batched)
+    table = SAMPLE_OUTPUTS if _sample_only else OUTPUTS
+    flags = dict(calc_normal=calc_normal, detailed=detailed_output or _sample_only, d_all=_sample_only)
 
     sdf_desc, sdf_packed = model.implicit_surface.nr_packed(dev)
     rad_desc, rad_packed = model.radiance_net.nr_packed(dev)
-    t_march = _linspace_table(N_STEPS, dev)
-    # perturb: bin edges linspace(0, 1, N+1) (unisurf.py:159, :188)
-    t_query = _linspace_table(N_query + (1 if perturb else 0), dev)
-    t_free = _linspace_table(N_freespace + (1 if perturb else 0), dev)
-
-    rgb = torch.empty(n, 3, device=dev) if not _sample_only else None
-    depth = torch.empty(n, device=dev) if not _sample_only else None
-    acc = torch.empty(n, device=dev) if not _sample_only else None
-    normals = torch.empty(n, 3, device=dev) if calc_normal and not _sample_only else None
-    det = {}
-    if _sample_only:  # training's no-grad pass: sample depths + surface points only
-        det = dict(surface_points=torch.empty(n, 3, device=dev),
-                   mask_surface=torch.empty(n, dtype=torch.bool, device=dev), depth_surface=torch.empty(n, device=dev),
-                   d_all=torch.empty(n, P, device=dev))
-    elif detailed_output:
-        det = dict(surface_points=torch.empty(n, 3, device=dev), mask_surface=torch.empty(n, dtype=torch.bool,
-                                                                                           device=dev),
-                   depth_surface=torch.empty(n, device=dev), radiance=torch.empty(n, P, 3, device=dev),
-                   implicit_surface=torch.empty(n, P, device=dev), implicit_nablas=torch.empty(n, P, 3, device=dev),
-                   alpha=torch.empty(n, P, device=dev), visibility_weights=torch.empty(n, P, device=dev))
     a = L.NrUnisurfArgs()
-    a.rays_o, a.rays_d, a.n_rays, a.rays_per_batch = L.ptr(ro), L.ptr(rd), n, N
+    a.rays_o, a.rays_d, a.n_rays, a.rays_per_batch = L.ptr(ro), L.ptr(rd), n, n // B
     a.sdf, a.sdf_packed = ctypes.pointer(sdf_desc), L.ptr(sdf_packed)
     a.rad, a.rad_packed = ctypes.pointer(rad_desc), L.ptr(rad_packed)
     a.logit_tau = float(logit_tau)
     a.radius_of_interest, a.interval = float(radius_of_interest), float(interval)
     a.too_close_threshold = float(too_close_threshold)
-    a.near_bypass = float('nan') if near_bypass is None else float(near_bypass)
-    a.far_bypass = float('nan') if far_bypass is None else float(far_bypass)
+    a.near_bypass, a.far_bypass = bypass(near_bypass), bypass(far_bypass)
     a.N_steps, a.N_secant_steps, a.N_query, a.N_freespace = N_STEPS, N_SECANT_STEPS, N_query, N_freespace
     a.no_secant = int(method != 'secant')  # ray_casting.py:128-135: any other method reports depth 1 on hits
     # F.normalize(nablas) with dim=1: per point for [chunk, 3] inputs, per window for [B, chunk, 3]
@@ -159,20 +150,14 @@ def volume_render(rays_o, rays_d, model, batched=False, batched_info={}, calc_no
     a.rayschunk, a.netchunk = int(rayschunk), int(netchunk)
     a.calc_normal, a.white_bkgd = int(bool(calc_normal)), int(bool(white_bkgd))
     a.full_march = int(bool(_full_march))
-    a.t_march, a.t_query, a.t_free = L.ptr(t_march), L.ptr(t_query), L.ptr(t_free)
-    a.rgb, a.depth, a.acc, a.normals = L.ptr(rgb), L.ptr(depth), L.ptr(acc), L.ptr(normals)
-    a.surface_points = L.ptr(det.get('surface_points'))
-    a.mask_surface = L.ptr(det.get('mask_surface'))
-    a.depth_surface = L.ptr(det.get('depth_surface'))
-    a.radiance_out = L.ptr(det.get('radiance'))
-    a.sdf_out = L.ptr(det.get('implicit_surface'))
-    a.nablas_out = L.ptr(det.get('implicit_nablas'))
-    a.alpha_out = L.ptr(det.get('alpha'))
-    a.weights_out = L.ptr(det.get('visibility_weights'))
-    if _sample_only:
-        a.d_all_out, a.sample_only = L.ptr(det['d_all']), 1
+    # perturb: bin edges linspace(0, 1, N+1) (unisurf.py:159, :188)
+    a.t_march = L.ptr(_linspace_table(N_STEPS, dev))
+    a.t_query = L.ptr(_linspace_table(N_query + (1 if perturb else 0), dev))
+    a.t_free = L.ptr(_linspace_table(N_freespace + (1 if perturb else 0), dev))
+    out = alloc_outputs(table, n, dict(P=N_query + N_freespace), flags, dev)
+    bind_outputs(table, a, out)
+    a.sample_only = int(_sample_only)
     if perturb:
-        B = rays_d.shape[0] if batched else 1
         u_q, u_f = _unisurf_uniforms(B, n // B, batched, int(rayschunk), N_query, N_freespace, dev)
         a.u_query, a.u_free = L.ptr(u_q), L.ptr(u_f)
     lib = L.lib()
@@ -180,34 +165,15 @@ def volume_render(rays_o, rays_d, model, batched=False, batched_info={}, calc_no
     if shard is not None and batched:
         ray0, row_rays, group = shard
         a.shard_ray0, a.shard_row_rays = int(ray0), int(row_rays)
-        B = rays_d.shape[0]
         window_ss = torch.zeros(B, max(int(lib.nr_unisurf_window_count(ctypes.byref(a))), 1), 3,
                                 dtype=torch.float64, device=dev)
         keep = _window_reducer(window_ss, group)
         a.window_ss, a.window_reduce = L.ptr(window_ss), ctypes.cast(keep, ctypes.c_void_p)
-    ws_bytes = lib.nr_unisurf_workspace_bytes(ctypes.byref(a))
-    if ws_bytes == 0:
-        raise NotImplementedError('neurecon_amd: ' + lib.nr_last_error().decode())
-    ws = L.workspace(dev, ws_bytes)
-    a.workspace, a.workspace_bytes = L.ptr(ws), ws_bytes
-    L.check(lib.nr_unisurf_render(ctypes.byref(a), L.stream_of(dev)))
+    run(lib.nr_unisurf_workspace_bytes, lib.nr_unisurf_render, a, dev)
     del keep
     if _sample_only:
-        return det
-
-    ret = OrderedDict([('rgb', rgb.reshape(*prefix, 3)), ('depth_volume', depth.reshape(prefix)),
-                       ('mask_volume', acc.reshape(prefix))])
-    if calc_normal:
-        ret['normals_volume'] = normals.reshape(*prefix, 3)
-    if detailed_output:
-        ret['surface_points'] = det['surface_points'].reshape(*prefix, 3)
-        ret['mask_surface'] = det['mask_surface'].reshape(prefix)
-        ret['depth_surface'] = det['depth_surface'].reshape(prefix)
-        ret['radiance'] = det['radiance'].reshape(*prefix, P, 3)
-        ret['implicit_surface'] = det['implicit_surface'].reshape(*prefix, P)
-        ret['implicit_nablas'] = det['implicit_nablas'].reshape(*prefix, P, 3)
-        ret['alpha'] = det['alpha'].reshape(*prefix, P)
-        ret['visibility_weights'] = det['visibility_weights'].reshape(*prefix, P)
+        return out
+    ret = extras_of(table, out, prefix, flags)
     return ret['rgb'], ret['depth_volume'], ret
 
 
@@ -238,9 +204,6 @@ def _train_render(rays_o, rays_d, model, batched, calc_normal, logit_tau, use_vi
     the integration as neurecon_amd.training autograd functions.  Returns (rgb, depth, extras)."""
     from .. import training as T
     check_view_dirs(model, use_view_dirs)
-    dev = rays_o.device
-    B = rays_d.shape[0] if batched else 1
-    prefix = [B, -1] if batched else [-1]
     P = N_query + N_freespace
     with torch.no_grad():
         ex = volume_render(rays_o, rays_d, model, batched=batched, logit_tau=logit_tau, use_view_dirs=use_view_dirs,
@@ -248,17 +211,9 @@ def _train_render(rays_o, rays_d, model, batched, calc_normal, logit_tau, use_vi
                            far_bypass=far_bypass, radius_of_interest=radius_of_interest, perturb=perturb,
                            interval=interval, too_close_threshold=too_close_threshold, N_query=N_query,
                            N_freespace=N_freespace, _sample_only=True)
-    ro = rays_o.reshape(-1, 3).float().contiguous()
-    rd_raw = rays_d.reshape(-1, 3).float().contiguous()
-    n = ro.shape[0]
+    ro, rd_raw, n, B, prefix = flat_rays(rays_o, rays_d, batched)
     d_all = ex['d_all']
-    rd = torch.empty_like(rd_raw)  # F.normalize(rays_d, dim=-1) (unisurf.py:118)
-    L.check(L.lib().nr_normalize3(L.ptr(rd_raw), n, L.ptr(rd), L.stream_of(dev)))
-    pts = torch.empty(n, P, 3, device=dev)
-    mids = torch.empty(n, P - 1, 3, device=dev)
-    dmid = torch.empty(n, P - 1, device=dev)
-    L.check(L.lib().nr_neus_points(L.ptr(ro), L.ptr(rd), L.ptr(d_all), n, P, L.ptr(pts), L.ptr(mids), L.ptr(dmid),
-                                   L.stream_of(dev)))
+    rd, pts, _, _ = train_points(ro, rd_raw, d_all)  # F.normalize(rays_d, dim=-1) (unisurf.py:118)
     logits, nablas, feat = T.sdf_nablas(model.implicit_surface, pts.reshape(-1, 3), True)   # unisurf.py:35
     nrm = _window_normalize(nablas.reshape(n, P, 3), batched, B, int(rayschunk), int(netchunk))
     view = rd[:, None, :].expand(n, P, 3).reshape(-1, 3).contiguous()
@@ -266,21 +221,11 @@ def _train_render(rays_o, rays_d, model, batched, calc_normal, logit_tau, use_vi
     rgb, depth, acc, w, alpha = T.UnisurfComposite.apply(logits.reshape(n, P), rad.reshape(n, P, 3), d_all,
                                                          bool(white_bkgd))
     nablas = nablas.reshape(n, P, 3)
-    ret = OrderedDict([('rgb', rgb.reshape(*prefix, 3)), ('depth_volume', depth.reshape(prefix)),
-                       ('mask_volume', acc.reshape(prefix))])
+    out = dict(ex, rgb=rgb, depth_volume=depth, mask_volume=acc, radiance=rad.reshape(n, P, 3),
+               implicit_surface=logits.reshape(n, P), implicit_nablas=nablas, alpha=alpha, visibility_weights=w)
     if calc_normal:  # unisurf.py:249-253
-        nn_ = F.normalize(nablas, dim=-1)
-        ret['normals_volume'] = (nn_ * w[..., None]).sum(dim=-2).reshape(*prefix, 3)
-    if detailed_output:
-        ret['surface_points'] = ex['surface_points'].reshape(*prefix, 3)
-        ret['mask_surface'] = ex['mask_surface'].reshape(prefix)
-        ret['depth_surface'] = ex['depth_surface'].reshape(prefix)
-        ret['radiance'] = rad.reshape(*prefix, P, 3)
-        ret['implicit_surface'] = logits.reshape(*prefix, P)
-        ret['implicit_nablas'] = nablas.reshape(*prefix, P, 3)
-        ret['alpha'] = alpha.reshape(*prefix, P)
-        ret['visibility_weights'] = w.reshape(*prefix, P)
-        ret['d_all'] = d_all.reshape(*prefix, P)
+        out['normals_volume'] = normals_volume(nablas, w)
+    ret = extras_of(OUTPUTS, out, prefix, dict(calc_normal=calc_normal, detailed=detailed_output, d_all=True))
     return ret['rgb'], ret['depth_volume'], ret
 
 
@@ -290,43 +235,27 @@ def surface_perturbation(like, scale):
     return (torch.rand(like.shape, device=like.device) - 0.5) * 2. * scale
 
 
-class SingleRenderer(nn.Module):
+class SingleRenderer(_shell.SingleRenderer):
     """unisurf.py:286-291."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.model = model
-
-    def forward(self, rays_o, rays_d, **kwargs):
-        return volume_render(rays_o, rays_d, self.model, **kwargs)
+    render = staticmethod(volume_render)
 
 
 volume_render.window_sharded = True  # render_sharded passes `shard=` (cross-rank F.normalize windows)
 
 
-class Trainer(nn.Module):
+class Trainer(_shell.Trainer):
     """unisurf.py:294-351: one training step's forward -- random rays of the image, the render with a
     graph (neurecon_amd.training autograd functions on libnrhip.so), L1 rgb loss and the normal
     smoothness term on the root-finding surface points.  Returns OrderedDict(losses=..., extras=...)
     like the reference; train.py calls backward() on losses['total'] (under DDP the gradient
     all-reduce runs over RCCL)."""
-
-    def __init__(self, model, device_ids=[0], batched=True):
-        super().__init__()
-        self.model = model
-        self.renderer = SingleRenderer(model)
-        if len(device_ids) > 1:
-            self.renderer = nn.DataParallel(self.renderer, device_ids=device_ids, dim=1 if batched else 0)
-        self.device = device_ids[0]
+    Renderer = SingleRenderer
 
     def forward(self, args, indices, model_input, ground_truth, render_kwargs_train, it, device='cuda'):
         from ..config import as_cfg
         args = as_cfg(args)
-        intrinsics = model_input['intrinsics'].to(device)
-        c2w = model_input['c2w'].to(device)
-        rays_o, rays_d, select_inds = rend_util.get_rays(c2w, intrinsics, render_kwargs_train['H'],
-                                                         render_kwargs_train['W'], N_rays=args.data.N_rays)
-        target_rgb = rend_util.gather_rays(ground_truth['rgb'].to(device), select_inds)       # unisurf.py:319
+        rays_o, rays_d, select_inds, target_rgb, _ = self.rays_and_targets(                        # unisurf.py:319
+            args, model_input, ground_truth, render_kwargs_train, device, mask_ignore=False)
         interval = max(args.training.delta_max * np.exp(-it * args.training.delta_beta), args.training.delta_min)
         rgb, depth_v, extras = self.renderer(rays_o, rays_d, interval=interval, detailed_output=True,
                                              **render_kwargs_train)
@@ -340,10 +269,7 @@ class Trainer(nn.Module):
             _, nablas_perturb, _ = self.model.implicit_surface.forward_with_nablas(pts_neighbor)
             losses['loss_reg'] = args.training.w_reg * F.mse_loss(F.normalize(nablas_perturb, dim=-1),
                                                                   F.normalize(nablas_surface, dim=-1))
-        loss = 0
-        for v in losses.values():
-            loss += v
-        losses['total'] = loss
+        self.sum_losses(losses)
         extras['scalars'] = {'interval': torch.tensor([interval]).to(device)}
         return OrderedDict([('losses', losses), ('extras', extras)])
 
@@ -353,26 +279,7 @@ def get_model(args):
     from ..config import as_cfg
     args = as_cfg(args)
     model_config = {'W_geo_feat': args.model.setdefault('W_geometry_feature', 256)}
-    surface_cfg = {
-        'use_siren': args.model.surface.setdefault('use_siren', args.model.setdefault('use_siren', False)),
-        'embed_multires': args.model.surface.setdefault('embed_multires', 6),
-        'radius_init': args.model.surface.setdefault('radius_init', 1.0),
-        'geometric_init': args.model.surface.setdefault('geometric_init', True),
-        'D': args.model.surface.setdefault('D', 8),
-        'W': args.model.surface.setdefault('W', 256),
-        'skips': args.model.surface.setdefault('skips', [4]),
-    }
-    radiance_cfg = {
-        'use_siren': args.model.radiance.setdefault('use_siren', args.model.setdefault('use_siren', False)),
-        'embed_multires': args.model.radiance.setdefault('embed_multires', -1),
-        'embed_multires_view': args.model.radiance.setdefault('embed_multires_view', -1),
-        'use_view_dirs': args.model.radiance.setdefault('use_view_dirs', True),
-        'D': args.model.radiance.setdefault('D', 4),
-        'W': args.model.radiance.setdefault('W', 256),
-        'skips': args.model.radiance.setdefault('skips', []),
-    }
-    model_config['surface_cfg'] = surface_cfg
-    model_config['radiance_cfg'] = radiance_cfg
+    model_config['surface_cfg'], model_config['radiance_cfg'] = net_cfgs(args)
     model = UNISURF(**model_config)
     render_kwargs_train = {
         'batched': True,

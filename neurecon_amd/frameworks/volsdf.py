@@ -19,7 +19,9 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import rend_util
 from ..base import ImplicitSurface, NeRF, RadianceNet, check_view_dirs, wants_graph
-from .neus import _linspace_table
+from . import _shell
+from ._shell import (HEAD, _linspace_table, alloc_outputs, bind_outputs, extras_of, f32, flat_rays, net_cfgs,
+                     normals_volume, run, train_points)
 
 
 class VolSDF(nn.Module):
@@ -110,6 +112,24 @@ def _volsdf_uniforms(B, N, batched, rayschunk, N_importance, N_outside, dev):
     return u_rand, u_out
 
 
+# a render's outputs in the order of its extras (volsdf.py:514-548); S samples, M = S + N_outside after
+# the NeRF++ merge (volsdf.py:465-469), M1 = M - 1 intervals
+OUTPUTS = HEAD + [
+    ('implicit_surface', 'sdf_out', ('S',), f32, ('detailed',)),
+    ('implicit_nablas', 'nablas_out', ('S', 3), f32, ('detailed',)),
+    ('radiance', 'radiance_out', ('M', 3), f32, ('detailed',)),
+    ('alpha', 'alpha_out', ('M1',), f32, ('detailed',)),
+    ('p_i', 'p_out', ('M1',), f32, ('detailed',)),
+    ('visibility_weights', 'weights_out', ('M1',), f32, ('detailed',)),
+    ('d_vals', 'd_vals', ('M',), f32, ('detailed',)),
+    ('sigma', 'sigma_out', ('M',), f32, ('detailed',)),
+    ('beta_map', 'beta_map', (1,), f32, ('detailed',)),
+    ('iter_usage', 'iter_usage', (), f32, ('detailed',)),
+    ('sigma_out', 'sigma_bg', ('No',), f32, ('detailed', 'outside')),
+    ('radiance_out', 'radiance_bg', ('No', 3), f32, ('detailed', 'outside')),
+]
+
+
 def volume_render(rays_o, rays_d, model, near=0.0, far=6.0, obj_bounding_radius=3.0, batched=False,
                   batched_info={}, calc_normal=False, use_view_dirs=True, rayschunk=65536, netchunk=1048576,
                   white_bkgd=False, use_nerfplusplus=False, detailed_output=True, show_progress=False,
@@ -127,42 +147,19 @@ def volume_render(rays_o, rays_d, model, near=0.0, far=6.0, obj_bounding_radius=
                              epsilon=epsilon)
     check_view_dirs(model, use_view_dirs)
     dev = rays_o.device
-    prefix = [rays_d.shape[0], -1] if batched else [-1]
-    ro = rays_o.reshape(-1, 3).float().contiguous()
-    rd = rays_d.reshape(-1, 3).float().contiguous()
-    n = ro.shape[0]
+    ro, rd, n, B, prefix = flat_rays(rays_o, rays_d, batched)
     S = N_samples + N_importance
     N0 = 4 * N_samples
     No = int(N_outside) if use_nerfplusplus else 0
-    M = S + No  # samples after the NeRF++ merge (volsdf.py:465-469)
+    flags = dict(calc_normal=calc_normal, detailed=detailed_output, outside=No > 0)
 
     sdf_desc, sdf_packed = model.implicit_surface.nr_packed(dev)
     rad_desc, rad_packed = model.radiance_net.nr_packed(dev)
-    alpha_net, beta_net = _host_ab(model)
-    t_coarse = _linspace_table(N_samples, dev)
-    t_init = _linspace_table(N0, dev)
-    u_up = _linspace_table(N0 + 2, dev)
-    u_fine = _linspace_table(N_importance, dev)
-
-    rgb = torch.empty(n, 3, device=dev)
-    depth = torch.empty(n, device=dev)
-    acc = torch.empty(n, device=dev)
-    normals = torch.empty(n, 3, device=dev) if calc_normal else None
-    det = {}
-    if detailed_output:
-        det = dict(implicit_surface=torch.empty(n, S, device=dev), implicit_nablas=torch.empty(n, S, 3, device=dev),
-                   radiance=torch.empty(n, M, 3, device=dev), alpha=torch.empty(n, M - 1, device=dev),
-                   p_i=torch.empty(n, M - 1, device=dev), visibility_weights=torch.empty(n, M - 1, device=dev),
-                   d_vals=torch.empty(n, M, device=dev), sigma=torch.empty(n, M, device=dev),
-                   beta_map=torch.empty(n, device=dev), iter_usage=torch.empty(n, device=dev))
-        if No > 0:
-            det['sigma_out'] = torch.empty(n, No, device=dev)
-            det['radiance_out'] = torch.empty(n, No, 3, device=dev)
     a = L.NrVolsdfArgs()
     a.rays_o, a.rays_d, a.n_rays = L.ptr(ro), L.ptr(rd), n
     a.sdf, a.sdf_packed = ctypes.pointer(sdf_desc), L.ptr(sdf_packed)
     a.rad, a.rad_packed = ctypes.pointer(rad_desc), L.ptr(rad_packed)
-    a.alpha_net, a.beta_net = alpha_net, beta_net
+    a.alpha_net, a.beta_net = _host_ab(model)
     a.beta_plus_init = _beta_plus_init(far, N0, epsilon) if No == 0 else 0.0
     if No > 0:
         nerf_desc, nerf_packed = model.nerf_outside.nr_packed(dev)
@@ -180,52 +177,18 @@ def volume_render(rays_o, rays_d, model, near=0.0, far=6.0, obj_bounding_radius=
     a.N_samples, a.N_importance = N_samples, N_importance
     a.max_upsample_steps, a.max_bisection_steps = max_upsample_steps, max_bisection_steps
     a.calc_normal, a.white_bkgd = int(bool(calc_normal)), int(bool(white_bkgd))
-    a.t_coarse, a.t_init, a.u_up, a.u_fine = L.ptr(t_coarse), L.ptr(t_init), L.ptr(u_up), L.ptr(u_fine)
-    a.rgb, a.depth, a.acc, a.normals = L.ptr(rgb), L.ptr(depth), L.ptr(acc), L.ptr(normals)
-    a.d_vals = L.ptr(det.get('d_vals'))
-    a.sdf_out = L.ptr(det.get('implicit_surface'))
-    a.nablas_out = L.ptr(det.get('implicit_nablas'))
-    a.radiance_out = L.ptr(det.get('radiance'))
-    a.alpha_out = L.ptr(det.get('alpha'))
-    a.p_out = L.ptr(det.get('p_i'))
-    a.weights_out = L.ptr(det.get('visibility_weights'))
-    a.sigma_out = L.ptr(det.get('sigma'))
-    a.beta_map = L.ptr(det.get('beta_map'))
-    a.iter_usage = L.ptr(det.get('iter_usage'))
-    a.sigma_bg = L.ptr(det.get('sigma_out'))
-    a.radiance_bg = L.ptr(det.get('radiance_out'))
+    a.t_coarse, a.t_init = L.ptr(_linspace_table(N_samples, dev)), L.ptr(_linspace_table(N0, dev))
+    a.u_up, a.u_fine = L.ptr(_linspace_table(N0 + 2, dev)), L.ptr(_linspace_table(N_importance, dev))
+    out = alloc_outputs(OUTPUTS, n, dict(S=S, M=S + No, M1=S + No - 1, No=No), flags, dev)
+    bind_outputs(OUTPUTS, a, out)
     if perturb:
         if _uniforms is None:
-            Bn = rays_d.shape[0] if batched else 1
-            _uniforms = _volsdf_uniforms(Bn, n // Bn, batched, int(rayschunk), N_importance, No, dev)
+            _uniforms = _volsdf_uniforms(B, n // B, batched, int(rayschunk), N_importance, No, dev)
         u_rand, u_out = _uniforms
         a.u_rand, a.u_out = L.ptr(u_rand), L.ptr(u_out)
     lib = L.lib()
-    ws_bytes = lib.nr_volsdf_workspace_bytes(ctypes.byref(a))
-    if ws_bytes == 0:
-        raise NotImplementedError('neurecon_amd: ' + lib.nr_last_error().decode())
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    a.workspace, a.workspace_bytes = L.ptr(ws), ws_bytes
-    L.check(lib.nr_volsdf_render(ctypes.byref(a), L.stream_of(dev)))
-
-    ret = OrderedDict([('rgb', rgb.reshape(*prefix, 3)), ('depth_volume', depth.reshape(prefix)),
-                       ('mask_volume', acc.reshape(prefix))])
-    if calc_normal:
-        ret['normals_volume'] = normals.reshape(*prefix, 3)
-    if detailed_output:
-        ret['implicit_surface'] = det['implicit_surface'].reshape(*prefix, S)
-        ret['implicit_nablas'] = det['implicit_nablas'].reshape(*prefix, S, 3)
-        ret['radiance'] = det['radiance'].reshape(*prefix, M, 3)
-        ret['alpha'] = det['alpha'].reshape(*prefix, M - 1)
-        ret['p_i'] = det['p_i'].reshape(*prefix, M - 1)
-        ret['visibility_weights'] = det['visibility_weights'].reshape(*prefix, M - 1)
-        ret['d_vals'] = det['d_vals'].reshape(*prefix, M)
-        ret['sigma'] = det['sigma'].reshape(*prefix, M)
-        ret['beta_map'] = det['beta_map'].reshape(*prefix, 1)
-        ret['iter_usage'] = det['iter_usage'].reshape(prefix)
-        if No > 0:
-            ret['sigma_out'] = det['sigma_out'].reshape(*prefix, No)
-            ret['radiance_out'] = det['radiance_out'].reshape(*prefix, No, 3)
+    run(lib.nr_volsdf_workspace_bytes, lib.nr_volsdf_render, a, dev)
+    ret = extras_of(OUTPUTS, out, prefix, flags)
     return ret['rgb'], ret['depth_volume'], ret
 
 
@@ -245,16 +208,12 @@ def _train_render(rays_o, rays_d, model, near=0.0, far=6.0, obj_bounding_radius=
     from .. import training as T
     check_view_dirs(model, use_view_dirs)
     dev = rays_o.device
-    prefix = [rays_d.shape[0], -1] if batched else [-1]
     No = int(N_outside) if use_nerfplusplus else 0
-    ro = rays_o.reshape(-1, 3).float().contiguous()
-    rd_raw = rays_d.reshape(-1, 3).float().contiguous()
-    n = ro.shape[0]
+    ro, rd_raw, n, B, prefix = flat_rays(rays_o, rays_d, batched)
     S = N_samples + N_importance
     uni = None
     if perturb:  # drawn once: the no-grad sampler and the background radii below use the same draws
-        Bn = rays_d.shape[0] if batched else 1
-        uni = _volsdf_uniforms(Bn, n // Bn, batched, int(rayschunk), N_importance, No, dev)
+        uni = _volsdf_uniforms(B, n // B, batched, int(rayschunk), N_importance, No, dev)
     with torch.no_grad():
         _, _, ex = volume_render(rays_o, rays_d, model, near=near, far=far, obj_bounding_radius=obj_bounding_radius,
                                  batched=batched, calc_normal=False, use_view_dirs=use_view_dirs, rayschunk=rayschunk,
@@ -264,13 +223,7 @@ def _train_render(rays_o, rays_d, model, near=0.0, far=6.0, obj_bounding_radius=
                                  epsilon=epsilon, _uniforms=uni)
     d_vals = ex['d_vals'].reshape(n, S + No)
     d_all = d_vals[:, :S].contiguous()
-    rd = torch.empty_like(rd_raw)  # F.normalize(rays_d, dim=-1) (volsdf.py:386)
-    L.check(L.lib().nr_normalize3(L.ptr(rd_raw), n, L.ptr(rd), L.stream_of(dev)))
-    pts = torch.empty(n, S, 3, device=dev)
-    mids = torch.empty(n, S - 1, 3, device=dev)
-    dmid = torch.empty(n, S - 1, device=dev)
-    L.check(L.lib().nr_neus_points(L.ptr(ro), L.ptr(rd), L.ptr(d_all), n, S, L.ptr(pts), L.ptr(mids), L.ptr(dmid),
-                                   L.stream_of(dev)))
+    rd, pts, _, _ = train_points(ro, rd_raw, d_all)  # F.normalize(rays_d, dim=-1) (volsdf.py:386)
     sdf, nablas, feat = T.sdf_nablas(model.implicit_surface, pts.reshape(-1, 3), True)      # volsdf.py:450
     view = rd[:, None, :].expand(n, S, 3).reshape(-1, 3).contiguous()
     rad = T.radiance(model.radiance_net, pts.reshape(-1, 3), view, nablas, feat)
@@ -294,29 +247,16 @@ def _train_render(rays_o, rays_d, model, near=0.0, far=6.0, obj_bounding_radius=
     rgb, depth, acc, tau, sdf_bg, p_i, sigma = T.VolSDFComposite.apply(
         sdf.reshape(n, S), beta, rad.reshape(n, S, 3), pts, d_all, bool(model.use_sphere_bg),
         float(model.obj_bounding_radius), bool(white_bkgd), *bg)
-    M = S + No
     nablas = nablas.reshape(n, S, 3)
-    ret = OrderedDict([('rgb', rgb.reshape(*prefix, 3)), ('depth_volume', depth.reshape(prefix)),
-                       ('mask_volume', acc.reshape(prefix))])
+    out = dict(rgb=rgb, depth_volume=depth, mask_volume=acc, implicit_surface=sdf_bg, implicit_nablas=nablas,
+               radiance=rad.reshape(n, S, 3) if No == 0 else torch.cat([rad.reshape(n, S, 3), bg[1]], 1),
+               alpha=1.0 - p_i, p_i=p_i, visibility_weights=tau, d_vals=d_vals, sigma=sigma,
+               beta_map=ex['beta_map'].reshape(n, 1), iter_usage=ex['iter_usage'].reshape(n))
+    if No > 0:
+        out.update(sigma_out=bg[0], radiance_out=bg[1])
     if calc_normal:  # volsdf.py:508-512
-        nrm = F.normalize(nablas, dim=-1)
-        k = min(tau.shape[-1], nrm.shape[-2])
-        ret['normals_volume'] = (nrm[:, :k, :] * tau[:, :k, None]).sum(dim=-2).reshape(*prefix, 3)
-    if detailed_output:
-        ret['implicit_surface'] = sdf_bg.reshape(*prefix, S)
-        ret['implicit_nablas'] = nablas.reshape(*prefix, S, 3)
-        radiances = rad.reshape(n, S, 3) if No == 0 else torch.cat([rad.reshape(n, S, 3), bg[1]], 1)
-        ret['radiance'] = radiances.reshape(*prefix, M, 3)
-        ret['alpha'] = (1.0 - p_i).reshape(*prefix, M - 1)
-        ret['p_i'] = p_i.reshape(*prefix, M - 1)
-        ret['visibility_weights'] = tau.reshape(*prefix, M - 1)
-        ret['d_vals'] = d_vals.reshape(*prefix, M)
-        ret['sigma'] = sigma.reshape(*prefix, M)
-        ret['beta_map'] = ex['beta_map'].reshape(*prefix, 1)
-        ret['iter_usage'] = ex['iter_usage'].reshape(prefix)
-        if No > 0:
-            ret['sigma_out'] = bg[0].reshape(*prefix, No)
-            ret['radiance_out'] = bg[1].reshape(*prefix, No, 3)
+        out['normals_volume'] = normals_volume(nablas, tau)
+    ret = extras_of(OUTPUTS, out, prefix, dict(calc_normal=calc_normal, detailed=detailed_output, outside=No > 0))
     return ret['rgb'], ret['depth_volume'], ret
 
 
@@ -326,42 +266,24 @@ def eikonal_points(like, bound):
     return torch.empty_like(like).uniform_(-bound, bound)
 
 
-class SingleRenderer(nn.Module):
+class SingleRenderer(_shell.SingleRenderer):
     """volsdf.py:555-561."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.model = model
-
-    def forward(self, rays_o, rays_d, **kwargs):
-        return volume_render(rays_o, rays_d, self.model, **kwargs)
+    render = staticmethod(volume_render)
 
 
-class Trainer(nn.Module):
+class Trainer(_shell.Trainer):
     """volsdf.py:564-640: one training step's forward -- random rays of the image, the render with a
     graph (neurecon_amd.training autograd functions on libnrhip.so), L1 rgb + eikonal losses (the
     nabla of each ray's highest-weight sample and one uniform point per ray).  Returns
     OrderedDict(losses=..., extras=...) like the reference; train.py calls backward() on
     losses['total'] (under DDP the gradient all-reduce runs over RCCL)."""
-
-    def __init__(self, model, device_ids=[0], batched=True):
-        super().__init__()
-        self.model = model
-        self.renderer = SingleRenderer(model)
-        if len(device_ids) > 1:
-            self.renderer = nn.DataParallel(self.renderer, device_ids=device_ids, dim=1 if batched else 0)
-        self.device = device_ids[0]
+    Renderer = SingleRenderer
 
     def forward(self, args, indices, model_input, ground_truth, render_kwargs_train, it, device='cuda'):
         from ..config import as_cfg
         args = as_cfg(args)
-        intrinsics = model_input['intrinsics'].to(device)
-        c2w = model_input['c2w'].to(device)
-        H, W = render_kwargs_train['H'], render_kwargs_train['W']
-        rays_o, rays_d, select_inds = rend_util.get_rays(c2w, intrinsics, H, W, N_rays=args.data.N_rays)
-        target_rgb = rend_util.gather_rays(ground_truth['rgb'].to(device), select_inds)      # volsdf.py:588
-        mask_ignore = rend_util.gather_rays(model_input['mask_ignore'].to(device), select_inds) \
-            if 'mask_ignore' in model_input else None
+        rays_o, rays_d, select_inds, target_rgb, mask_ignore = self.rays_and_targets(               # volsdf.py:588
+            args, model_input, ground_truth, render_kwargs_train, device)
         rgb, depth_v, extras = self.renderer(rays_o, rays_d, detailed_output=True, **render_kwargs_train)
         nablas = extras['implicit_nablas']
         # one point per ray: the sample of highest visibility weight (volsdf.py:604-605)
@@ -379,10 +301,7 @@ class Trainer(nn.Module):
             losses['loss_img'] = (losses['loss_img'] * mask_ignore[..., None].float()).sum() / (mask_ignore.sum() + 1e-10)
         else:
             losses['loss_img'] = losses['loss_img'].mean()
-        loss = 0
-        for k, v in losses.items():
-            loss += losses[k]
-        losses['total'] = loss
+        self.sum_losses(losses)
         extras['implicit_nablas_norm'] = nablas_norm
         alpha, beta = self.model.forward_ab()
         extras['scalars'] = {'beta': beta.data, 'alpha': alpha.data}
@@ -401,26 +320,7 @@ def get_model(args):
         'speed_factor': args.training.setdefault('speed_factor', 1.0),
         'beta_init': args.training.setdefault('beta_init', 0.1),
     }
-    surface_cfg = {
-        'use_siren': args.model.surface.setdefault('use_siren', args.model.setdefault('use_siren', False)),
-        'embed_multires': args.model.surface.setdefault('embed_multires', 6),
-        'radius_init': args.model.surface.setdefault('radius_init', 1.0),
-        'geometric_init': args.model.surface.setdefault('geometric_init', True),
-        'D': args.model.surface.setdefault('D', 8),
-        'W': args.model.surface.setdefault('W', 256),
-        'skips': args.model.surface.setdefault('skips', [4]),
-    }
-    radiance_cfg = {
-        'use_siren': args.model.radiance.setdefault('use_siren', args.model.setdefault('use_siren', False)),
-        'embed_multires': args.model.radiance.setdefault('embed_multires', -1),
-        'embed_multires_view': args.model.radiance.setdefault('embed_multires_view', -1),
-        'use_view_dirs': args.model.radiance.setdefault('use_view_dirs', True),
-        'D': args.model.radiance.setdefault('D', 4),
-        'W': args.model.radiance.setdefault('W', 256),
-        'skips': args.model.radiance.setdefault('skips', []),
-    }
-    model_config['surface_cfg'] = surface_cfg
-    model_config['radiance_cfg'] = radiance_cfg
+    model_config['surface_cfg'], model_config['radiance_cfg'] = net_cfgs(args)
     model = VolSDF(**model_config)
     render_kwargs_train = {
         'near': args.data.near,

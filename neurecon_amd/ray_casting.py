@@ -73,7 +73,7 @@ def root_finding_surface_points(surface_query_fn, rays_o, rays_d, near=0.0, far=
     skips the refinement and reports depth 1 on hits (ray_casting.py:128-135).  The march runs in
     chunks of 32 steps over the rays without a sign change so far; _full_march=True evaluates every
     step of every ray (the reference's schedule, the same outputs bit for bit)."""
-    from .frameworks.neus import _linspace_table
+    from .frameworks._shell import _linspace_table
     if not hasattr(surface_query_fn, 'nr_packed'):
         raise NotImplementedError('neurecon_amd: root finding needs a neurecon_amd ImplicitSurface as surface_query_fn')
     L.require_gpu(rays_o, 'rays_o')
