@@ -708,6 +708,52 @@ int nr_nn_query(int64_t N, const float* queries, int64_t M, double max_dist, int
                 int64_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image metrics of rendered frames on the device (nr_imgmetrics.hip): the error sums behind PSNR and the
+ * depth L1 / RMSE, SSIM, and the cosine between two normal maps; the image half of a published result
+ * (NeuS and VolSDF report the PSNR of rendered views).  Every output is a pure function of the inputs,
+ * float64 with each operation rounded on its own and every sum a fixed tree (no float atomics): two runs
+ * are bit-identical and tests/image_metrics_ref.py restates the three rules in numpy.  The rules in full,
+ * the order of the sums and the LDS budget of the SSIM kernel: the header comment of the file.
+ *
+ * pred, gt fp32 [F, H, W, C], contiguous, channel last, 1 <= C <= 4; mask uint8 [F, H, W] or NULL (a
+ * pixel passes when its byte is not 0); F, H, W >= 1, F H W C < 2^31.  Every entry checks its arguments
+ * before any HIP call: NR_ERR_ARG for a null required pointer, C outside 1..4, win even or outside
+ * 1..33, a null window, F H W C >= 2^31; NR_ERR_WORKSPACE (as everywhere in this library) for a null or
+ * too small workspace.
+ *   nr_img_workspace_bytes   8 x max(4 F ceil(H W / 2048), 3 F ceil(H / TH) ceil(W / 32)) rounded up to
+ *                            256, TH = min(32, 64512 / (8 (31 + win) + 1280) - (win - 1)) the tile rows
+ *                            of the SSIM kernel (0 on a bad argument).  Non-decreasing in every argument;
+ *                            nr_img_error needs the first term only (any valid win covers it).
+ *   nr_img_error             a pixel counts iff it passes the mask and all 2 C of its values are finite; one
+ *                            that passes the mask with a non-finite value is excluded.  Per counted value
+ *                            d = (double)p - (double)g.  out (device float64 [F, 4]) = {sum d d, sum |d|,
+ *                            n_used, n_excluded}, the counts in pixels.  C = 3: PSNR; C = 1: depth L1 / RMSE.
+ *   nr_img_ssim              Wang et al. 2004 per channel, population covariances, valid region only.
+ *                            window: device float64 [win]; C1, C2 finite, >= 0.  At (r, c), r <= H - win,
+ *                            c <= W - win, for each field a of {x, y, x x, y y, x y} (products of the widened
+ *                            fp32 values: exact): h[j] = sum_i w[i] a[r + j, c + i], then m = sum_j w[j] h[j],
+ *                            each sum sequential in ascending tap order from w[0] a[0], every product and
+ *                            addition rounded separately.  vx = exx - mx mx, vy = eyy - my my, cxy = exy - mx my,
+ *                            S = ((2 (mx my) + C1) (2 cxy + C2)) / (((mx mx + my my) + C1) ((vx + vy) + C2)).
+ *                            map (float64 [F, H - win + 1, W - win + 1, C], or NULL) = S; NaN exactly where the
+ *                            window covers a non-finite input.  out (device float64 [F, 3]) = {sum S, n_used,
+ *                            n_nan} over the map values whose centre pixel (r + win / 2, c + win / 2) passes the
+ *                            mask: those that are not NaN are summed and counted in n_used, the NaN ones in
+ *                            n_nan.  H < win or W < win: an empty map, out = 0, no error.
+ *   nr_img_normal_cos        a, b fp32 [P, 3] (3 P < 2^31), mask uint8 [P] or NULL, out float64 [P]:
+ *                            dot = (ax bx + ay by) + az bz, na, nb likewise, cos = dot / sqrt(na nb) clamped
+ *                            to [-1, 1]; NaN where the mask is 0, a value is not finite or na nb == 0.  Needs
+ *                            no workspace.
+ * ------------------------------------------------------------------------------------------ */
+size_t nr_img_workspace_bytes(int64_t F, int64_t H, int64_t W, int64_t C, int64_t win);
+int nr_img_error(const float* pred, const float* gt, const uint8_t* mask, int64_t F, int64_t H, int64_t W, int64_t C,
+                 double* out, void* workspace, size_t workspace_bytes, void* stream);
+int nr_img_ssim(const float* pred, const float* gt, const uint8_t* mask, int64_t F, int64_t H, int64_t W, int64_t C,
+                const double* window, int64_t win, double C1, double C2, double* map, double* out, void* workspace,
+                size_t workspace_bytes, void* stream);
+int nr_img_normal_cos(const float* a, const float* b, const uint8_t* mask, int64_t P, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training path (models/frameworks/neus.py:417-485, models/base.py:265-282 with
  * create_graph=True).  The host runs the step layer by layer: the dense [P, K] x [K, N] layer
  * products go to hipBLASLt, every per-point / per-ray step between them is one of these kernels.

@@ -250,8 +250,14 @@ _SIGS = {
     'nr_nn_bounds': (_c_i, [_c_p, _c_i64, _c_p, _c_p, _c_sz, _c_p]),
     'nr_nn_build': (_c_i, [_c_p, _c_i64, _c_d, _c_p, _c_sz, _c_p]),
     'nr_nn_query': (_c_i, [_c_i64, _c_p, _c_i64, _c_d, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    # image metrics: PSNR / depth error sums, SSIM, normal cosine (nr_imgmetrics.hip)
+    'nr_img_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
+    'nr_img_error': (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p]),
+    'nr_img_ssim': (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_d, _c_d, _c_p, _c_p,
+                           _c_p, _c_sz, _c_p]),
+    'nr_img_normal_cos': (_c_i, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     # training path (nr_train.hip)
-    'nr_embed': (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_p]),
+    'nr_embed':(_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_jvp': (_c_i, [_c_p, _c_p, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_vjp': (_c_i, [_c_p, _c_p, _c_i, _c_p, _c_i, _c_f, _c_i64, _c_i, _c_p, _c_p]),
     'nr_embed_padded': (_c_i, [_c_p, _c_i64, _c_i, _c_p, _c_i, _c_p]),
