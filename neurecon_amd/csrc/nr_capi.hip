@@ -68,7 +68,9 @@ SdfLayout sdf_layout(const NrSdfDesc& d) {
   }
   static_assert(sdf_op_off(kSdfOps - 1) + (kSdfNBO[kSdfOps - 1] / 2) * (2 * kSdfKB[kSdfOps - 1] + 1) * 1024 > 0, "");
   L.scale_off = (uint32_t)off;
-  off = align256(off + kSdfOps * 4);
+  L.winv_off = L.scale_off + 128;  // inside scale_off's 256 bytes: the pack's size and offsets stay
+  static_assert(kSdfOps * 4 <= 128, "max |W| and 1 / weight scale share 256 bytes");
+  off = align256(off + 128 + kSdfOps * 4);
   L.bound_off = (uint32_t)off;
   off = align256(off + kSdfOps * 8);
   L.w8row0_off = (uint32_t)off;
@@ -267,6 +269,8 @@ int nr_sdf_pack(const NrSdfDesc* d, const float* const* W, const float* const* b
   ops[B0] = mkop(W[0], nullptr, ROWS(0), in0, 1, seg(4, 0, in0), none(), seg(16, 0, 256), none(), 1.0f, prec, wmax + B0);
   float* bound = (float*)(P + L.bound_off);
   for (int i = 0; i < kSdfOps; ++i) ops[i].bound = bound + 2 * i;
+  // per-op scalar table of the lean ops (sdf4_kernel's reverse pass): 1 / weight scale beside (R, B)
+  for (int i = 0; i < kSdfOps; ++i) ops[i].winv = (float*)(P + L.winv_off) + i;
   ops[F7].aux = W[8];  // sdf row W8[0, :] rides with F7's chunks (F7Epi4's running dot product)
   char* dst[kSdfOps];
   for (int i = 0; i < kSdfOps; ++i) dst[i] = P + L.op_off[i];

@@ -44,6 +44,8 @@ struct SdfLayout {
   uint32_t op_off[kSdfOps];
   uint32_t op_bytes[kSdfOps];  // bytes of one chunk of the op
   uint32_t scale_off;          // [kSdfOps] max |W| per op (f16x3 weight scaling)
+  uint32_t winv_off;           // [kSdfOps] 1 / weight scale per op (word 32 of the op's bias slots), in the
+                               // second half of scale_off's 256 bytes: sdf4_kernel's lean (reverse) ops
   uint32_t bound_off;          // [kSdfOps][2] max row L1 norm, max |bias| per op (f16x3 operand scales)
   uint32_t w8row0_off;         // sdf row of the last layer [256]
   uint32_t misc_off;           // [0] = sdf bias
@@ -120,6 +122,7 @@ struct PackOp {
   const float* bias2;  //   ... and its bias
   int64_t wn2;
   int ld2;
+  float* winv;         // optional: device word receiving 1 / weight scale (what bias-slot float 32 holds)
 };
 
 int launch_pack_op(const PackOp& op, char* dst, hipStream_t stream);

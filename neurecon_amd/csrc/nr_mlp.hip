@@ -285,6 +285,8 @@ __device__ __forceinline__ float act_bwd(float g, float e) {
 
 // chunk = [A: 2*KB KB][bias slot: 32 floats (2 output blocks), [32] = 1/weight-scale; 1 KB]
 __host__ __device__ constexpr int chunk_bytes(int KB) { return (2 * KB + 1) * 1024; }
+// ... without the bias slot: what a lean op (op4) fetches of each chunk
+__host__ __device__ constexpr int weight_bytes(int KB) { return 2 * KB * 1024; }
 
 // ---------------------------------------------------------------------------------------------
 // split-fp16 x3 operands: v = (hi + lo) * 2^-k with hi = f16(v 2^k), lo = f16(v 2^k - hi).
@@ -898,6 +900,7 @@ struct Pend4 {
 
 constexpr int kSlabRing = 3;  // softplus' slabs in LDS: one being read, one landing, one being staged
 constexpr int kFwdRing = 4;   // weight-ring slots of the forward-only sdf4_kernel launches
+constexpr int kTabBytes = 8 * 512;  // one op's bias table: 8 chunks x 512 B (WStream4::dma_tab)
 // cache policy of the forward softplus slab stores (read back by the reverse pass of the same tile)
 constexpr bool kSlabNT = true;
 // ... of the geometry-feature and d sdf / d z7 stores
@@ -920,6 +923,8 @@ struct WStream4 {
   int es;      // slab slot the next stage_slab() writes
   int er;      // slab slot the next consumed chunk's epilogue reads
   int prev;    // RING 4: VMEM instructions this wave issued in the previous chunk iteration
+  char* tab;   // bias table (op4's kTab mode): 2 buffers x kTabBytes, or null
+  int tcur;    // table buffer of the op being computed
   __device__ __forceinline__ static int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
   __device__ __forceinline__ static int next3(int i) { return i == 2 ? 0 : i + 1; }
   __device__ __forceinline__ static int nextr(int i) { return i == RING - 1 ? 0 : i + 1; }
@@ -993,13 +998,44 @@ struct WStream4 {
     wait_vmcnt(npieces<B1>());
     __syncthreads();
   }
+  // The bias table of one op: the first 512 B (float4 0..31: bias, scalars, aux, TS bias) of the bias slot
+  // of each of its chunks, entry c at c x 512.  One instruction moves two entries: lanes 0-31 read chunk
+  // 2p's slot, lanes 32-63 chunk 2p+1's (per-lane source, lane-linear destination).  Every loader wave
+  // issues one: wave w pair w & 3 (waves 4-7: identical bytes to the same address), 8 entries in all (a
+  // 7-chunk op's last entry is the following op's first bytes, inside the pack and never read).
+  // gop: the op's first chunk, CBN its chunk stride.
+  template <int CBN>
+  __device__ __forceinline__ void dma_tab(const char* gop, int buf) {
+    const int wave = loader();
+    if (wave < 0) return;
+    const uint32_t l = threadIdx.x & 63;
+    const uint32_t voff = (l & 31) * 16 + (l >> 5) * (uint32_t)CBN;
+    const int pair = wave & 3;
+    const char* g = uniform_ptr(gop) + (CBN - 1024) + pair * 2 * CBN;
+    const uint32_t base =
+        __builtin_amdgcn_readfirstlane(lds_u32(tab) + (uint32_t)(buf * kTabBytes) + (uint32_t)(pair * 1024));
+    glds16m(g, voff, base);
+  }
+  __device__ __forceinline__ static int ntab() { return loader() >= 0 ? 1 : 0; }
+  // entry c of the op being computed
+  __device__ __forceinline__ const float4* tab_entry(int c) const {
+    uint32_t off = tcur * kTabBytes;
+    asm volatile("" : "+s"(off));
+    return (const float4*)(tab + off + c * 512);
+  }
   template <int B0, int B1, int B2>
-  __device__ __forceinline__ void start(const char* g0, const char* g1, const char* g2) {
+  __device__ __forceinline__ void start(const char* g0, const char* g1, const char* g2) { start<B0, B1, B2, 0>(g0, g1, g2, nullptr); }
+  // CBT != 0: also the bias table of the first op (gt, chunk stride CBT), behind chunk 0 and ahead of the
+  // chunks the wait leaves in flight
+  template <int B0, int B1, int B2, int CBT>
+  __device__ __forceinline__ void start(const char* g0, const char* g1, const char* g2, const char* gt) {
     static_assert(RING == 4, "start: the first RING - 1 chunks");
     cur = 0;
     es = 0;
     er = 0;
+    tcur = 0;
     dma<B0>(g0, 0);
+    if constexpr (CBT != 0) dma_tab<CBT>(gt, 0);
     dma<B1>(g1, 1);
     dma<B2>(g2, 2);
     prev = npieces<B2>();
@@ -1148,12 +1184,30 @@ __device__ __forceinline__ void stamp_add(int ph, uint64_t dt) {
 #define NR_STAMP(var)
 #endif
 
-template <int KB, int NBO, int NXT_CB, bool AUX, bool TS, class WS, class Pre, class Epi>
+// MODE: where the op's bias-slot data comes from (NXT_MODE: the same for the next op, whose first chunks
+// this op issues).
+// kSlot: the whole chunk is fetched and the bias slot read from the ring slot.
+// kLean: the op has no per-row data in its bias slots (transposed ops: no bias, no aux).  Only the 2 KB
+// weight pieces of each chunk are fetched, from the unchanged global address (the chunk stride stays
+// CB) into the unchanged ring slot, so every loader wave issues 2 KB / kLd pieces and none twice for
+// KB 16; the op's one scalar, 1 / weight scale, comes in as winv (per-op table of the pack's tail).
+// kTab (forward ops of the launches whose LDS holds the weight ring alone): the chunks are fetched as in
+// kLean; bias, scalars and aux come from the op's bias table in LDS (WStream4::dma_tab), fetched once
+// per op by the op before it, in the iteration that issues this op's chunk 0 (start() for the first
+// op), into the table buffer the op before that one has left.
+enum { kSlot = 0, kLean = 1, kTab = 2 };
+template <int KB, int NBO, int NXT_CB, bool AUX, bool TS, int MODE = kSlot, int NXT_MODE = kSlot, class WS,
+          class Pre, class Epi>
 __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const char* nxt, const f16x8 (&bh)[kNC][12],
                                     const f16x8 (&bl)[kNC][12], const float (&xinv)[kNC], Pend4& pd, Pre&& pre,
-                                    Epi&& epi, int lane) {
+                                    Epi&& epi, int lane, float winv = 0.0f) {
   constexpr int CB = chunk_bytes(KB);
+  constexpr bool LEAN = MODE == kLean;
+  constexpr int FB = MODE != kSlot ? weight_bytes(KB) : CB;             // bytes fetched per chunk
+  constexpr int NXT_FB = NXT_MODE != kSlot ? NXT_CB - 1024 : NXT_CB;    // ... of the next op
+  static_assert(!LEAN || (!AUX && !TS), "lean ops carry no per-row data");
   constexpr int NCH = NBO / 2;
+  static_assert(MODE != kTab || NCH * 512 <= kTabBytes, "bias table entries");
   constexpr int LA = WS::kRingN - 1;  // chunks issued ahead of the one being computed
   static_assert(NCH >= 2, "the 2-ahead stream needs >= 2 chunks per op");
   // (a 4-slot ring's lookahead reaches chunk 2 of the next op: forward ops only, all >= 7 chunks)
@@ -1168,11 +1222,17 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
     NR_STAMP(t0);
     int npend = 0;
     if (c + LA < NCH) {
-      ws.template issue<CB>(opc + (c + LA) * CB);
-      npend = WS::template npieces<CB>();
+      ws.template issue<FB>(opc + (c + LA) * CB);
+      npend = WS::template npieces<FB>();
     } else if (nxc) {
-      ws.template issue<NXT_CB>(nxc + (c + LA - NCH) * NXT_CB);
-      npend = WS::template npieces<NXT_CB>();
+      ws.template issue<NXT_FB>(nxc + (c + LA - NCH) * NXT_CB);
+      npend = WS::template npieces<NXT_FB>();
+      if constexpr (NXT_MODE == kTab) {
+        if (c + LA == NCH) {  // (compile time) the next op's chunk 0 went out just now: its table with it
+          ws.template dma_tab<NXT_CB>(nxc, ws.tcur ^ 1);
+          npend += WS::ntab();
+        }
+      }
     }
     npend += pre(c);
     // the previous chunk's stores go out after this chunk's DMA: this chunk's flip does not wait for
@@ -1190,9 +1250,18 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
       }
     });
     NR_STAMP(t2);
-    float wi = A[2 * KB * 64 + 8].x;
-    if constexpr (TS) wi *= kT;
-    const float4 b0 = A[2 * KB * 64 + (TS ? 24 : 0) + g], b1 = A[2 * KB * 64 + (TS ? 28 : 4) + g];
+    float wi;
+    float4 b0, b1;
+    if constexpr (LEAN) {  // + 0 kept: an accumulator of -0 comes out +0, as with the slot's zero bias
+      wi = winv;
+      b0 = b1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      const float4* S = MODE == kTab ? ws.tab_entry(c) : A + 2 * KB * 64;  // the chunk's bias slot
+      wi = S[8].x;
+      if constexpr (TS) wi *= kT;
+      b0 = S[(TS ? 24 : 0) + g];
+      b1 = S[(TS ? 28 : 4) + g];
+    }
 #pragma unroll
     for (int q = 0; q < kNC; ++q) {
       const float inv = xinv[q] * wi;
@@ -1200,8 +1269,9 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
       zq.z[q][1] = fma4s(acc[q][1], inv, b1);
     }
     if constexpr (AUX) {
-      zq.aux[0] = A[2 * KB * 64 + 16 + g];
-      zq.aux[1] = A[2 * KB * 64 + 20 + g];
+      const float4* S = MODE == kTab ? ws.tab_entry(c) : A + 2 * KB * 64;
+      zq.aux[0] = S[16 + g];
+      zq.aux[1] = S[20 + g];
     }
 #ifdef NR_EXP_STAMPS
     wait_vmcnt(npend);
@@ -1218,6 +1288,7 @@ __device__ __forceinline__ void op4(WS& ws, const char* __restrict__ op, const c
 #endif
   }
   pd.flush();  // chunk NCH-2's stores, put by its epilogue in the last iteration
+  if constexpr (MODE == kTab) ws.tcur ^= 1;  // the next op's table
 #pragma unroll
   for (int e = 0; e < 8; ++e) epi(NCH - 1, zq, e);
 }
@@ -1468,9 +1539,15 @@ void sdf4_kernel(SdfKArgs a) {
   static_assert((size_t)kW4 * kNC * kSlabColBytes <= kScratchPerWG, "per-workgroup slab scratch");
   constexpr bool SLABS = NABLA && STAGE != 1;
   constexpr int RING = SLABS ? 3 : kFwdRing;
-  __shared__ __attribute__((aligned(16))) char smem[RING * CB + (SLABS ? kSlabRing * kSlab4 : 0)];
-  static_assert(RING * CB + (SLABS ? kSlabRing * kSlab4 : 0) <= 160 * 1024, "LDS budget");
-  WStream4<CB, RING, NW> ws{smem, SLABS ? smem + RING * CB : nullptr, 0, 0, 0, 0};
+  // the launches without a slab ring have room for the forward ops' bias table beside the weight ring
+  // (4 x 37 KB + 2 x 4 KB): their forward ops run in op4's kTab mode, the others' on the slot path
+  constexpr bool TABF = !SLABS;
+  constexpr int FM = TABF ? kTab : kSlot;  // mode of the forward ops
+  constexpr int LDSB = RING * CB + (SLABS ? kSlabRing * kSlab4 : 0) + (TABF ? 2 * kTabBytes : 0);
+  __shared__ __attribute__((aligned(16))) char smem[LDSB];
+  static_assert(LDSB <= 160 * 1024, "LDS budget");
+  static_assert(!TABF || RING * CB + 2 * kTabBytes == LDSB, "the bias table follows the weight ring");
+  WStream4<CB, RING, NW> ws{smem, SLABS ? smem + RING * CB : nullptr, 0, 0, 0, 0, TABF ? smem + RING * CB : nullptr, 0};
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = lane & 15, g = lane >> 4;
   const char* W = a.packed;
@@ -1502,8 +1579,14 @@ void sdf4_kernel(SdfKArgs a) {
   if ((threadIdx.x & 63) == 0)
     for (int i = 0; i < kStampPh; ++i) stamp_lds()[wave * kStampPh + i] = 0;
 #endif
-  if constexpr (STAGE == 2) ws.template start<C16, C16>(OP(B7), OP(B7) + C16);
-  else if constexpr (RING == 4) ws.template start<C4, C4, C4>(OP(F0), OP(F0) + C4, OP(F0) + 2 * C4);
+  // The reverse ops run in op4's kLean mode (no bias piece) in the reverse-only launches and in the
+  // nabla + feature launch.  The fused nabla launch without the feature keeps the slot path: lean, it
+  // spills 59 registers instead of 24 (profiles/lean_stream/registers.txt).
+  constexpr bool LEANR = STAGE == 2 || (NABLA && FEAT);
+  constexpr int W16 = weight_bytes(16);  // a lean chunk of B7
+  if constexpr (STAGE == 2) ws.template start<W16, W16>(OP(B7), OP(B7) + C16);
+  else if constexpr (TABF)
+    ws.template start<weight_bytes(4), weight_bytes(4), weight_bytes(4), C4>(OP(F0), OP(F0) + C4, OP(F0) + 2 * C4, OP(F0));
   else ws.template start<C4, C4>(OP(F0), OP(F0) + C4);
   Pend4 pd{};
   NoPre4 nopre;
@@ -1565,11 +1648,27 @@ void sdf4_kernel(SdfKArgs a) {
     float mrun[kNC], m_in[kNC];  // running max |output| of the op being computed (lane's values),
                                  // max |input| of the op being computed (per point)
     // (R, B) of the op about to run ride in its chunks' bias slot (floats 33, 34); its chunk 0 is
-    // the current ring slot when it starts
+    // the current ring slot when it starts (TABF: entry 0 of its bias table, current since the op
+    // before it ended)
     auto next_scales = [&](int kb, float extra, const float (&floor_max)[kNC], float (&sc)[kNC]) {
-      const float4 v = ws.buf()[2 * kb * 64 + 8];
+      const float4 v = TABF ? ws.tab_entry(0)[8] : ws.buf()[2 * kb * 64 + 8];
 #pragma unroll
       for (int q = 0; q < kNC; ++q) sc[q] = bound_scale(fmaxf(fmaf(v.y, m_in[q], v.z) + extra, floor_max[q]));
+    };
+    // The reverse ops fetch no bias slot (op4's kLean mode): their three scalars -- 1 / weight scale and
+    // (R, B), the words 32..34 of every one of their slots -- come from the per-op tables of the pack's
+    // tail through a wave-uniform pointer (scalar loads, as b8), one op ahead of their use.
+    struct OpScal {
+      float winv, R, B;
+    };
+    auto op_scal = [&](int opi) {
+      const char* w = W;
+      asm volatile("" : "+s"(w));
+      // constant address space: scalar loads wherever they stand (the pack is not written while a
+      // render kernel runs), never a vector load that a counted vmcnt wait would have to count
+      typedef __attribute__((address_space(4))) const float cfloat;
+      cfloat* rb = (cfloat*)(w + a.L.bound_off + 8 * opi);
+      return OpScal{*(cfloat*)(w + a.L.winv_off + 4 * opi), rb[0], rb[1]};
     };
     // end of an op: its output becomes the next operand; mscale converts the running max to output
     // units (forward softplus epilogues track max(L, t), i.e. y / (ln2/100))
@@ -1628,26 +1727,26 @@ void sdf4_kernel(SdfKArgs a) {
     {
       float sc[kNC];
       next_scales(4, kSpSlack, zero2, sc);
-      op4<4, 16, C16, false, true>(ws, OP(F0), OP(F1), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(0)), lane);
+      op4<4, 16, C16, false, true, FM, FM>(ws, OP(F0), OP(F1), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(0)), lane);
       finish(sc, kC);
     }
     {
       float sc[kNC];
       next_scales(16, kSpSlack, zero2, sc);
-      op4<16, 16, C16, false, true>(ws, OP(F1), OP(F2), Vh, Vl, xinv, pd, nopre, fwd_epi(Uh, Ul, sc, slab(1)), lane);
+      op4<16, 16, C16, false, true, FM, FM>(ws, OP(F1), OP(F2), Vh, Vl, xinv, pd, nopre, fwd_epi(Uh, Ul, sc, slab(1)), lane);
       finish(sc, kC);
     }
     {
       float sc[kNC];
       next_scales(16, kSpSlack, zero2, sc);
-      op4<16, 16, C16, false, true>(ws, OP(F2), OP(F3), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(2)), lane);
+      op4<16, 16, C16, false, true, FM, FM>(ws, OP(F2), OP(F3), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(2)), lane);
       finish(sc, kC);
     }
     {
       // F3's outputs (h3: 217 rows in 14 blocks) and the embedding form F4's operand: one scale
       float sc[kNC];
       next_scales(16, kSpSlack, mE, sc);
-      op4<16, 14, C18, false, true>(ws, OP(F3), OP(F4), Vh, Vl, xinv, pd, nopre, fwd_epi(Uh, Ul, sc, slab(3)), lane);
+      op4<16, 14, C18, false, true, FM, FM>(ws, OP(F3), OP(F4), Vh, Vl, xinv, pd, nopre, fwd_epi(Uh, Ul, sc, slab(3)), lane);
       if constexpr (NABLA) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -1666,19 +1765,19 @@ void sdf4_kernel(SdfKArgs a) {
     {
       float sc[kNC];
       next_scales(18, kSpSlack, zero2, sc);
-      op4<18, 16, C16, false, true>(ws, OP(F4), OP(F5), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(4)), lane);
+      op4<18, 16, C16, false, true, FM, FM>(ws, OP(F4), OP(F5), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(4)), lane);
       finish(sc, kC);
     }
     {
       float sc[kNC];
       next_scales(16, kSpSlack, zero2, sc);
-      op4<16, 16, C16, false, true>(ws, OP(F5), OP(F6), Vh, Vl, xinv, pd, nopre, fwd_epi(Uh, Ul, sc, slab(5)), lane);
+      op4<16, 16, C16, false, true, FM, FM>(ws, OP(F5), OP(F6), Vh, Vl, xinv, pd, nopre, fwd_epi(Uh, Ul, sc, slab(5)), lane);
       finish(sc, kC);
     }
     {
       float sc[kNC];
       next_scales(16, kSpSlack, zero2, sc);
-      op4<16, 16, C16, false, true>(ws, OP(F6), OP(F7), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(6)), lane);
+      op4<16, 16, C16, false, true, FM, FM>(ws, OP(F6), OP(F7), Uh, Ul, xinv, pd, nopre, fwd_epi(Vh, Vl, sc, slab(6)), lane);
       finish(sc, kC);
     }
     // F7: softplus, sdf row (aux = W8[0, :]) as a running dot product, d sdf / d z7 parked in slab 7,
@@ -1694,7 +1793,8 @@ void sdf4_kernel(SdfKArgs a) {
       const char* n;
       if constexpr (FEAT) n = OPF8();
       else n = (NABLA && STAGE == 0) ? OP(B7) : (has_next ? OP(F0) : nullptr);
-      op4<16, 16, NXT, true, false>(ws, OP(F7), n, Vh, Vl, xinv, pd, nopre, epi, lane);
+      // next: F8 (forward), B7 (here only on the slot path: LEANR needs FEAT), or the next tile's F0
+      op4<16, 16, NXT, true, false, FM, FM>(ws, OP(F7), n, Vh, Vl, xinv, pd, nopre, epi, lane);
       finish(sc);
     }
 #pragma unroll
@@ -1724,7 +1824,8 @@ void sdf4_kernel(SdfKArgs a) {
       };
       constexpr int NXT = NABLA ? C16 : C4;
       const char* n = NABLA ? OP(B7) : (has_next ? OP(F0) : nullptr);
-      op4<16, 16, NXT, false, false>(ws, OPF8(), n, Uh, Ul, xinv, pd, nopre, epi, lane);
+      op4<16, 16, NXT, false, false, FM, NABLA ? (LEANR ? kLean : kSlot) : FM>(ws, OPF8(), n, Uh, Ul, xinv, pd, nopre, epi,
+                                                                               lane);
     }
     }  // STAGE != 2: forward
     if constexpr (NABLA && STAGE == 1) {  // the slabs stay for the reverse-pass launch
@@ -1734,6 +1835,8 @@ void sdf4_kernel(SdfKArgs a) {
       // ---- reverse pass (autograd.grad of sdf w.r.t. x, base.py:265-282) ------------------------
       pd.flush();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      OpScal osn{};  // the scalars of the op about to run, loaded while the previous one runs
+      if constexpr (LEANR) osn = op_scal(B7);
       float4* g7 = slab(7);
 #pragma unroll
       for (int q = 0; q < kNC; ++q) {  // d sdf / d z7 from slab 7, split with the exact max scale
@@ -1757,13 +1860,21 @@ void sdf4_kernel(SdfKArgs a) {
       // NMAIN/2 are embedding gradients, parked in fp32
       if constexpr (COMPACT) ws.stage_slab(slab(6), 0, soff);  // B7's chunk 0 (consumed in B7's second iteration)
       else ws.stage_slab(slab(6), 0);
-      auto bwd = [&](auto kb_tag, auto nbo_tag, auto nmain_tag, auto nxt_tag, int opi, const char* nxt,
+      auto bwd = [&](auto kb_tag, auto nbo_tag, auto nmain_tag, auto nxt_tag, auto nxl_tag, int opi, const char* nxt,
                      f16x8(&ih)[kNC][12], f16x8(&il)[kNC][12], f16x8(&oh)[kNC][12], f16x8(&ol)[kNC][12], int lcur,
                      int park_blk, int lnext) {
         constexpr int KBo = decltype(kb_tag)::value, NBOo = decltype(nbo_tag)::value;
         constexpr int NMAIN = decltype(nmain_tag)::value, NXC = decltype(nxt_tag)::value;
+        constexpr bool NXL = decltype(nxl_tag)::value;
+        const OpScal os = osn;
         float sc[kNC];
-        next_scales(KBo, 0.0f, zero2, sc);
+        if constexpr (LEANR) {
+          if (opi != B0) osn = op_scal(opi + 1);  // B7..B0 are consecutive in stream order
+#pragma unroll
+          for (int q = 0; q < kNC; ++q) sc[q] = bound_scale(fmaxf(fmaf(os.R, m_in[q], os.B) + 0.0f, zero2[q]));
+        } else {
+          next_scales(KBo, 0.0f, zero2, sc);
+        }
         auto pre = [&](int c) -> int {
           if constexpr (COMPACT) {
             if (2 * (c + 1) < NMAIN) return ws.stage_slab(slab(lcur), c + 1, soff);
@@ -1775,7 +1886,8 @@ void sdf4_kernel(SdfKArgs a) {
           return 0;
         };
         BwdEpi4<NMAIN, decltype(ws)> epi{oh, ol, sc, ws, park, park_blk, mrun, pd, lane, COMPACT ? plane : lane};
-        op4<KBo, NBOo, NXC, false, false>(ws, OP(opi), nxt, ih, il, xinv, pd, pre, epi, lane);
+        constexpr int RM = LEANR ? kLean : kSlot, RMN = (LEANR && NXL) ? kLean : kSlot;
+        op4<KBo, NBOo, NXC, false, false, RM, RMN>(ws, OP(opi), nxt, ih, il, xinv, pd, pre, epi, lane, os.winv);
         finish(sc);
       };
       using I0 = std::integral_constant<int, 0>;
@@ -1786,16 +1898,18 @@ void sdf4_kernel(SdfKArgs a) {
       using IC16 = std::integral_constant<int, C16>;
       using IC14 = std::integral_constant<int, C14>;
       using IC4 = std::integral_constant<int, C4>;
-      bwd(I16{}, I16{}, I16{}, IC16{}, B7, OP(B6), Uh, Ul, Vh, Vl, 6, 0, 5);
-      bwd(I16{}, I16{}, I16{}, IC16{}, B6, OP(B5), Vh, Vl, Uh, Ul, 5, 0, 4);
-      bwd(I16{}, I16{}, I16{}, IC16{}, B5, OP(B4), Uh, Ul, Vh, Vl, 4, 0, 3);
+      using LeanNext = std::true_type;   // the next op is a reverse op too
+      using SlotNext = std::false_type;  // ... the next tile's F0
+      bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B7, OP(B6), Uh, Ul, Vh, Vl, 6, 0, 5);
+      bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B6, OP(B5), Vh, Vl, Uh, Ul, 5, 0, 4);
+      bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B5, OP(B4), Uh, Ul, Vh, Vl, 4, 0, 3);
       // skip layer: rows 0..216 -> h3 (scaled by softplus'(z3)), rows 217..255 -> embedding
-      bwd(I16{}, I18{}, I14{}, IC14{}, B4, OP(B3), Vh, Vl, Uh, Ul, 3, 0, 2);
-      bwd(I14{}, I16{}, I16{}, IC16{}, B3, OP(B2), Uh, Ul, Vh, Vl, 2, 0, 1);
-      bwd(I16{}, I16{}, I16{}, IC16{}, B2, OP(B1), Vh, Vl, Uh, Ul, 1, 0, 0);
-      bwd(I16{}, I16{}, I16{}, IC16{}, B1, OP(B0), Uh, Ul, Vh, Vl, 0, 0, -1);
-      if constexpr (STAGE == 2) bwd(I16{}, I4{}, I0{}, IC16{}, B0, has_next ? OP(B7) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
-      else bwd(I16{}, I4{}, I0{}, IC4{}, B0, has_next ? OP(F0) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
+      bwd(I16{}, I18{}, I14{}, IC14{}, LeanNext{}, B4, OP(B3), Vh, Vl, Uh, Ul, 3, 0, 2);
+      bwd(I14{}, I16{}, I16{}, IC16{}, LeanNext{}, B3, OP(B2), Uh, Ul, Vh, Vl, 2, 0, 1);
+      bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B2, OP(B1), Vh, Vl, Uh, Ul, 1, 0, 0);
+      bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B1, OP(B0), Uh, Ul, Vh, Vl, 0, 0, -1);
+      if constexpr (STAGE == 2) bwd(I16{}, I4{}, I0{}, IC16{}, LeanNext{}, B0, has_next ? OP(B7) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
+      else bwd(I16{}, I4{}, I0{}, IC4{}, SlotNext{}, B0, has_next ? OP(F0) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
       pd.flush();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       // chain rule through the positional encoding (autograd sums both uses of embed(x))
@@ -3439,11 +3553,13 @@ __device__ __forceinline__ float op_bias(const PackOp& op, int s, int row) {
 }
 
 // weight scale 2^(13 - e) for max |W| = f 2^e (f16x3), 1 for fp32
-__device__ __forceinline__ float wscale(const PackOp& op) {
-  if (op.prec != NR_PREC_F16X3) return 1.0f;
-  const float m = *op.wmax;
+__device__ __forceinline__ float wscale_of(int prec, float m) {
+  if (prec != NR_PREC_F16X3) return 1.0f;
   if (!(m > 0.0f)) return 1.0f;
   return __builtin_ldexpf(1.0f, 13 - __builtin_amdgcn_frexp_expf(m));
+}
+__device__ __forceinline__ float wscale(const PackOp& op) {
+  return wscale_of(op.prec, op.prec == NR_PREC_F16X3 ? *op.wmax : 0.0f);
 }
 
 // word e of a packed op
@@ -3645,6 +3761,8 @@ __global__ __launch_bounds__(256) void pack_final_kernel(PackBatch pb) {
       c = fmaxf(c, red[2][w]);
     }
     if (op.prec == NR_PREC_F16X3) *op.wmax = a;
+    // the bias slot's word 32 once per op (sdf4_kernel's lean ops read it here, not from the chunks)
+    if (op.winv) *op.winv = 1.0f / wscale_of(op.prec, a);
     if (op.bound) {
       op.bound[0] = b;
       op.bound[1] = c;
