@@ -565,6 +565,111 @@ __device__ __forceinline__ float wave_sum4(float v) {  // sum over the 4 lane-gr
   return v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// positional encoding of sdf4_kernel's render launches (6 bands: the only SDF net the library admits)
+// ---------------------------------------------------------------------------------------------
+// A point's 64 operand rows sit in its four lanes (lane group g holds rows 16 b + 4 g + r), and one
+// embed_feature / embed_backward call per row makes every lane run sinf and cosf 12 times for the 36
+// values the point has.  Here each of the point's 18 arguments a = 3 band + c is evaluated once, sin
+// and cos together, by lane group a & 3 in slot a >> 2 (5 calls per lane: 20 evaluations, the last two
+// of arguments no row has), and a row's value comes from the lane that holds it (ds_bpermute: no LDS
+// memory).  A launch with both passes evaluates them at the tile start and again at the tile end, as
+// before.  The values are sinf / cosf of the same fp32 argument as in embed_feature / embed_backward,
+// so they are theirs bit for bit.
+constexpr int kEncSlots = 5, kEncBands = 6;
+struct Enc4 {
+  float s[kEncSlots], c[kEncSlots];  // sin, cos of this lane's arguments g + 4 slot
+};
+__device__ __noinline__ float2 embed_sincos(float v) { return make_float2(sinf(v), cosf(v)); }
+__device__ __forceinline__ void enc_eval(Enc4& t, const float (&x)[3], int g) {
+  float x0 = x[0], x1 = x[1], x2 = x[2];
+  asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2));  // values in registers: selected below, not branched on
+#pragma unroll
+  for (int s = 0; s < kEncSlots; ++s) {
+    // a = 18, 19 (band 6): evaluated, fetched by no row
+    const uint32_t a = (uint32_t)g + 4u * s, band = (a * 11u) >> 5 /* a / 3, a < 22 */, c = a - 3u * band;
+    float xc = c == 1u ? x1 : x0;
+    xc = c == 2u ? x2 : xc;
+    const float2 r = embed_sincos(fmul(xc, __uint_as_float(0x3f800000u + (band << 23))));
+    t.s[s] = r.x;
+    t.c[s] = r.y;
+  }
+}
+// where row f's trig value is: lane group | slot << 2 | (cos ? 32 : 0), or 0xff for a row without one;
+// deriv: the value of its derivative instead (cos for a sin row, sin for a cos row)
+constexpr uint32_t enc_src(int f, bool deriv) {
+  const int fp = f - 3;
+  if (fp < 0 || fp >= 6 * kEncBands) return 0xffu;
+  const int band = fp / 6, m = fp % 6, a = band * 3 + m % 3;
+  return (uint32_t)((a & 3) | ((a >> 2) << 2) | (((m >= 3) != deriv) ? 32 : 0));
+}
+// what the chain rule needs of row f: coordinate | band << 2 | (cos row ? 32 : 0) | (raw coordinate ? 64 : 0),
+// or 0xff for a row that is always zero
+constexpr uint32_t enc_meta(int f) {
+  if (f < 3) return (uint32_t)(f | 64);
+  const int fp = f - 3;
+  if (fp >= 6 * kEncBands) return 0xffu;
+  const int band = fp / 6, m = fp % 6;
+  return (uint32_t)((m % 3) | (band << 2) | (m >= 3 ? 32 : 0));
+}
+// the value of row F0 + 4 g from the lane that evaluated it (0 where the row has none); j = lane & 15
+template <int F0, bool DERIV>
+__device__ __forceinline__ float enc_pull(const Enc4& t, int g, int j) {
+  constexpr uint32_t c0 = enc_src(F0, DERIV), c1 = enc_src(F0 + 4, DERIV), c2 = enc_src(F0 + 8, DERIV),
+                     c3 = enc_src(F0 + 12, DERIV);
+  constexpr uint32_t word = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+  const uint32_t code = (word >> (8 * g)) & 0xffu;
+  const int addr = (int)((((code & 3u) << 4) | (uint32_t)j) << 2);
+  float out = 0.0f;
+#pragma unroll
+  for (uint32_t id = 0; id < 16; ++id) {  // id = slot | (cos ? 8 : 0): only the ones some lane group asks for
+    if ((c0 >> 2) != id && (c1 >> 2) != id && (c2 >> 2) != id && (c3 >> 2) != id) continue;
+    const float src = (id & 8) ? t.c[id & 7] : t.s[id & 7];
+    const float v = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(src)));
+    out = (code >> 2) == id ? v : out;
+  }
+  return out;
+}
+// rows 16 b + 4 g + r of the encoding, r = 0..3 (embed_feature's values)
+template <int B>
+__device__ __forceinline__ float4 enc_rows(const Enc4& t, const float (&x)[3], int g, int j) {
+  if constexpr (16 * B + 3 >= 3 + 6 * kEncBands + 12) {  // no lane group has a row
+    float z = 0.0f;  // made per tile: a constant would be hoisted out of the tile loop into 4 more registers
+    asm volatile("" : "+v"(z));
+    return make_float4(z, z, z, z);
+  }
+  float v[4];
+  v[0] = enc_pull<16 * B + 0, false>(t, g, j);
+  v[1] = enc_pull<16 * B + 1, false>(t, g, j);
+  v[2] = enc_pull<16 * B + 2, false>(t, g, j);
+  v[3] = enc_pull<16 * B + 3, false>(t, g, j);
+  if constexpr (B == 0) {  // rows 0..2: the coordinates themselves
+#pragma unroll
+    for (int r = 0; r < 3; ++r) v[r] = g == 0 ? x[r] : v[r];
+  }
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
+// embed_backward for row F0 + 4 g: the same fmul / fadd on the same values, into the same n
+template <int F0>
+__device__ __forceinline__ void enc_row_bwd(const Enc4& t, float gf, int g, int j, float& n0, float& n1,
+                                            float& n2) {
+  constexpr uint32_t m0 = enc_meta(F0), m1 = enc_meta(F0 + 4), m2 = enc_meta(F0 + 8), m3 = enc_meta(F0 + 12);
+  if constexpr (m0 == 0xffu && m1 == 0xffu && m2 == 0xffu && m3 == 0xffu) return;
+  constexpr uint32_t word = m0 | (m1 << 8) | (m2 << 16) | (m3 << 24);
+  const uint32_t meta = (word >> (8 * g)) & 0xffu;
+  // d cos = -sin: the cos rows' bit 5 becomes the sign bit
+  const float tv = __uint_as_float(__float_as_uint(enc_pull<F0, true>(t, g, j)) ^ ((meta & 32u) << 26));
+  const float freq = __uint_as_float(0x3f800000u + (((meta >> 2) & 7u) << 23));
+  const float contrib = (meta & 64u) ? gf : fmul(fmul(gf, tv), freq);
+  // selects, not conditional stores (those get merged into one store through a selected pointer, which
+  // puts n0..n2 into scratch memory); a row that is always zero has c = 3 and adds to none
+  const uint32_t c = meta & 3u;
+  const float s0 = fadd(n0, contrib), s1 = fadd(n1, contrib), s2 = fadd(n2, contrib);
+  n0 = c == 0u ? s0 : n0;
+  n1 = c == 1u ? s1 : n1;
+  n2 = c == 2u ? s2 : n2;
+}
+
 // =============================================================================================
 // SDF kernel
 // =============================================================================================
@@ -1169,8 +1274,14 @@ constexpr float kC = 0.0069314749f;
 #ifdef NR_EXP_STAMPS
 // stamps build: per-wave shader-clock totals of the four phases of a chunk iteration (VMEM
 // issue, MFMA loop + epilogue stages, bias + vmcnt wait, barrier), copied out at the end of the launch
-constexpr int kStampPh = 6;  // 4 phases + iteration count (tgemm_kernel: tile start) + tgemm's epilogue
-__device__ unsigned long long g_nr_stamps[2048 * 8 * kStampPh];
+// sdf4_kernel also stamps the whole tile: 6 = tile start (loop top to the first op), 7 = tile end (last op's
+// return to the loop's end), 8 = the tile; what 8 has beyond 0..3, 6 and 7 is the op boundaries and the
+// forward -> reverse turn
+constexpr int kStampPh = 9;  // 4 phases + iteration count (tgemm_kernel: tile start) + tgemm's epilogue + 3
+constexpr int kStampSlot = 2048 * 8 * kStampPh;  // one launch's stamps
+// slot 0: the last launch of any stamped kernel; slot 1 + STAGE_: the last sdf4_kernel launch of that STAGE_
+// (a render runs several instances back to back)
+__device__ unsigned long long g_nr_stamps[6 * kStampSlot];
 __device__ __forceinline__ unsigned long long* stamp_lds() {
   __shared__ unsigned long long s_stamp[kW4 * kStampPh];
   return s_stamp;
@@ -1180,8 +1291,14 @@ __device__ __forceinline__ void stamp_add(int ph, uint64_t dt) {
   if ((threadIdx.x & 63) == 0) stamp_lds()[(threadIdx.x >> 6) * kStampPh + ph] += dt;
 }
 #define NR_STAMP(var) const uint64_t var = stamp_now()
+#define NR_STAMP_VAR(var) uint64_t var = 0
+#define NR_STAMP_SET(var) var = stamp_now()
+#define NR_STAMP_ADD(ph, dt) stamp_add(ph, dt)
 #else
 #define NR_STAMP(var)
+#define NR_STAMP_VAR(var)
+#define NR_STAMP_SET(var)
+#define NR_STAMP_ADD(ph, dt)
 #endif
 
 // MODE: where the op's bias-slot data comes from (NXT_MODE: the same for the next op, whose first chunks
@@ -1532,6 +1649,16 @@ void sdf4_kernel(SdfKArgs a) {
   static_assert(STAGE_ != 3 || (!NABLA && !FEAT), "narrow tiles: forward-only launches");
   static_assert(STAGE == 0 || (NABLA && !FEAT), "deferred nablas: no feature");
   constexpr int PPW = 16 * kNC * NW;  // points per workgroup tile
+  // positional encoding: one evaluation per argument (Enc4) in the render launches that run a reverse pass
+  // -- the mid-point launch <true, true, 0> and the reverse-only <true, false, 2 / 4>, whose chain rule stood
+  // bare at the tile end.  The forward-only instances keep one call per row (the sample launch measured no
+  // faster with Enc4: profiles/tile_turns/ab.txt), and so does the fused nabla launch without the feature,
+  // which holds the others to embed_feature's and embed_backward's values.
+#ifdef NR_EXP_ROW_ENC  // variant builds: every instance on the per-row calls, for an A/B of the encoding alone
+  constexpr bool ENC4 = false;
+#else
+  constexpr bool ENC4 = NABLA && STAGE != 1 && !(!FEAT && STAGE_ == 0);
+#endif
   constexpr int CB = chunk_bytes(18);  // largest SDF op chunk (F4: 14 + 4 input blocks)
   constexpr int C16 = chunk_bytes(16), C4 = chunk_bytes(4), C14 = chunk_bytes(14), C18 = chunk_bytes(18);
   // launches with a reverse pass share the LDS with the slab ring (3 weight slots); forward-only
@@ -1598,6 +1725,10 @@ void sdf4_kernel(SdfKArgs a) {
                                   : (a.P_dev ? min(a.P, (int64_t)(*a.P_dev) * a.P_mult) : a.P);
   for (int64_t base = (int64_t)blockIdx.x * PPW; base < Pn; base += (int64_t)gridDim.x * PPW) {
     const bool has_next = base + (int64_t)gridDim.x * PPW < Pn;
+    NR_STAMP_VAR(ts0);
+    NR_STAMP_VAR(ts1);  // the first op starts
+    NR_STAMP_VAR(te0);  // the last op has returned
+    NR_STAMP_SET(ts0);
     int64_t p0 = base + wave * 16 * kNC;  // this wave's first point
     int plane = lane;                      // float4 index of this lane's slab-7 / parked entries
     uint32_t soff = 0;                     // byte offset of this lane's slab codes (COMPACT)
@@ -1686,13 +1817,25 @@ void sdf4_kernel(SdfKArgs a) {
     if constexpr (STAGE != 2) {
 #pragma unroll
     for (int q = 0; q < kNC; ++q) {
+      if constexpr (ENC4) {
+        // lane group and column rebuilt opaquely: hoisted out of the tile loop, the rows' source lanes and
+        // select masks would sit in registers for the whole kernel
+        const int ge = (int)opaque_lane(g), je = (int)opaque_lane(j);
+        Enc4 t;
+        enc_eval(t, xs[q], ge);
+        E[q][0] = enc_rows<0>(t, xs[q], ge, je);
+        E[q][1] = enc_rows<1>(t, xs[q], ge, je);
+        E[q][2] = enc_rows<2>(t, xs[q], ge, je);
+        E[q][3] = enc_rows<3>(t, xs[q], ge, je);
+      } else {
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int f = 16 * b + 4 * g;
-        E[q][b] = make_float4(embed_feature(f + 0, xs[q][0], xs[q][1], xs[q][2], a.nfreq),
-                              embed_feature(f + 1, xs[q][0], xs[q][1], xs[q][2], a.nfreq),
-                              embed_feature(f + 2, xs[q][0], xs[q][1], xs[q][2], a.nfreq),
-                              embed_feature(f + 3, xs[q][0], xs[q][1], xs[q][2], a.nfreq));
+        for (int b = 0; b < 4; ++b) {
+          const int f = 16 * b + 4 * g;
+          E[q][b] = make_float4(embed_feature(f + 0, xs[q][0], xs[q][1], xs[q][2], a.nfreq),
+                                embed_feature(f + 1, xs[q][0], xs[q][1], xs[q][2], a.nfreq),
+                                embed_feature(f + 2, xs[q][0], xs[q][1], xs[q][2], a.nfreq),
+                                embed_feature(f + 3, xs[q][0], xs[q][1], xs[q][2], a.nfreq));
+        }
       }
       mE[q] = max4_groups(amax8(amax8(0.0f, E[q][0], E[q][1]), E[q][2], E[q][3]));
       const float sE = bound_scale(mE[q]);  // exact-max scale for the embedding operand of F0
@@ -1724,6 +1867,7 @@ void sdf4_kernel(SdfKArgs a) {
     };
 
     // ---- forward (base.py:243-257) -------------------------------------------------------------
+    NR_STAMP_SET(ts1);
     {
       float sc[kNC];
       next_scales(4, kSpSlack, zero2, sc);
@@ -1797,6 +1941,7 @@ void sdf4_kernel(SdfKArgs a) {
       op4<16, 16, NXT, true, false, FM, FM>(ws, OP(F7), n, Vh, Vl, xinv, pd, nopre, epi, lane);
       finish(sc);
     }
+    NR_STAMP_SET(te0);
 #pragma unroll
     for (int q = 0; q < kNC; ++q) {
       const float sdf = wave_sum4(sdf_part[q]) + b8;
@@ -1826,6 +1971,7 @@ void sdf4_kernel(SdfKArgs a) {
       const char* n = NABLA ? OP(B7) : (has_next ? OP(F0) : nullptr);
       op4<16, 16, NXT, false, false, FM, NABLA ? (LEANR ? kLean : kSlot) : FM>(ws, OPF8(), n, Uh, Ul, xinv, pd, nopre, epi,
                                                                                lane);
+      NR_STAMP_SET(te0);
     }
     }  // STAGE != 2: forward
     if constexpr (NABLA && STAGE == 1) {  // the slabs stay for the reverse-pass launch
@@ -1900,6 +2046,9 @@ void sdf4_kernel(SdfKArgs a) {
       using IC4 = std::integral_constant<int, C4>;
       using LeanNext = std::true_type;   // the next op is a reverse op too
       using SlotNext = std::false_type;  // ... the next tile's F0
+      if constexpr (STAGE == 2) {
+        NR_STAMP_SET(ts1);
+      }
       bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B7, OP(B6), Uh, Ul, Vh, Vl, 6, 0, 5);
       bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B6, OP(B5), Vh, Vl, Uh, Ul, 5, 0, 4);
       bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B5, OP(B4), Uh, Ul, Vh, Vl, 4, 0, 3);
@@ -1910,21 +2059,45 @@ void sdf4_kernel(SdfKArgs a) {
       bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B1, OP(B0), Uh, Ul, Vh, Vl, 0, 0, -1);
       if constexpr (STAGE == 2) bwd(I16{}, I4{}, I0{}, IC16{}, LeanNext{}, B0, has_next ? OP(B7) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
       else bwd(I16{}, I4{}, I0{}, IC4{}, SlotNext{}, B0, has_next ? OP(F0) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
+      NR_STAMP_SET(te0);
       pd.flush();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       // chain rule through the positional encoding (autograd sums both uses of embed(x))
 #pragma unroll
       for (int q = 0; q < kNC; ++q) {
         float n0 = 0.f, n1 = 0.f, n2 = 0.f;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
+        auto grad = [&](int b) {  // the gradient of rows 16 b + 4 g + r: skip layer's + first layer's
           const float4 u = fromf(*((const gf4*)park + (kNC * b + q) * 64 + (COMPACT ? plane : lane)));
           const float4 v = fromf(*((const gf4*)park + (kNC * (4 + b) + q) * 64 + (COMPACT ? plane : lane)));
-          const int f = 16 * b + 4 * g;
-          embed_backward(f + 0, fadd(v.x, u.x), xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
-          embed_backward(f + 1, fadd(v.y, u.y), xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
-          embed_backward(f + 2, fadd(v.z, u.z), xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
-          embed_backward(f + 3, fadd(v.w, u.w), xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
+          return make_float4(fadd(v.x, u.x), fadd(v.y, u.y), fadd(v.z, u.z), fadd(v.w, u.w));
+        };
+        if constexpr (ENC4) {  // rows in embed_backward's order
+          const int ge = (int)opaque_lane(g), je = (int)opaque_lane(j);  // (as at the tile start)
+          Enc4 t;
+          enc_eval(t, xs[q], ge);
+          const float4 g0 = grad(0), g1 = grad(1), g2 = grad(2);
+          enc_row_bwd<0>(t, g0.x, ge, je, n0, n1, n2);
+          enc_row_bwd<1>(t, g0.y, ge, je, n0, n1, n2);
+          enc_row_bwd<2>(t, g0.z, ge, je, n0, n1, n2);
+          enc_row_bwd<3>(t, g0.w, ge, je, n0, n1, n2);
+          enc_row_bwd<16>(t, g1.x, ge, je, n0, n1, n2);
+          enc_row_bwd<17>(t, g1.y, ge, je, n0, n1, n2);
+          enc_row_bwd<18>(t, g1.z, ge, je, n0, n1, n2);
+          enc_row_bwd<19>(t, g1.w, ge, je, n0, n1, n2);
+          enc_row_bwd<32>(t, g2.x, ge, je, n0, n1, n2);
+          enc_row_bwd<33>(t, g2.y, ge, je, n0, n1, n2);
+          enc_row_bwd<34>(t, g2.z, ge, je, n0, n1, n2);
+          enc_row_bwd<35>(t, g2.w, ge, je, n0, n1, n2);  // rows 48..63: none within 6 bands
+        } else {
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const float4 gr = grad(b);
+            const int f = 16 * b + 4 * g;
+            embed_backward(f + 0, gr.x, xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
+            embed_backward(f + 1, gr.y, xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
+            embed_backward(f + 2, gr.z, xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
+            embed_backward(f + 3, gr.w, xs[q][0], xs[q][1], xs[q][2], a.nfreq, n0, n1, n2);
+          }
         }
         n0 = wave_sum4(n0);
         n1 = wave_sum4(n1);
@@ -1937,13 +2110,20 @@ void sdf4_kernel(SdfKArgs a) {
         }
       }
     }
+    NR_STAMP(te1);
+    NR_STAMP_ADD(6, ts1 - ts0);
+    NR_STAMP_ADD(7, te1 - te0);
+    NR_STAMP_ADD(8, te1 - ts0);
   }
   pd.flush();
   wait_vmcnt(0);  // a block without tiles still has the prologue's second chunk in flight
 #ifdef NR_EXP_STAMPS
   if ((threadIdx.x & 63) == 0 && blockIdx.x < 2048)
-    for (int i = 0; i < kStampPh; ++i)
-      g_nr_stamps[(blockIdx.x * kW4 + wave) * kStampPh + i] = stamp_lds()[wave * kStampPh + i];
+    for (int i = 0; i < kStampPh; ++i) {
+      const unsigned long long v = stamp_lds()[wave * kStampPh + i];
+      g_nr_stamps[(blockIdx.x * kW4 + wave) * kStampPh + i] = v;
+      g_nr_stamps[(1 + STAGE_) * kStampSlot + (blockIdx.x * kW4 + wave) * kStampPh + i] = v;
+    }
 #endif
 }
 
@@ -3835,6 +4015,8 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
   const int grid = grid_for(P);
   NR_REQUIRE(!f8_alt || (feature && L.prec == NR_PREC_F16X3 && !L.siren), NR_ERR_ARG,
              "sdf: an op in F8's place needs the f16x3 softplus net and a feature buffer");
+  NR_REQUIRE(L.siren || L.prec != NR_PREC_F16X3 || nfreq == kEncBands, NR_ERR_UNSUPPORTED,
+             "sdf: the f16x3 softplus net encodes 6 bands");
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, feature, (float4*)ws, nfreq, P_dev, P_mult, nullptr, nullptr,
              nullptr, (const char*)f8_alt};
   ProfScope prof(nabla ? (feature ? "sdf_nabla_feat" : "sdf_nabla") : (feature ? "sdf_feat" : "sdf_fwd"), (double)P,
@@ -3879,6 +4061,7 @@ int launch_sdf_deferred(const SdfLayout& L, const void* packed, const float* pts
                         int nfreq, float4* slabs, const int* tiles, const int* n_tiles, int stage, hipStream_t stream) {
   if (P <= 0) return NR_OK;
   NR_REQUIRE(L.prec == NR_PREC_F16X3 && !L.siren, NR_ERR_UNSUPPORTED, "deferred nablas: f16x3 softplus nets");
+  NR_REQUIRE(nfreq == kEncBands, NR_ERR_UNSUPPORTED, "sdf: the f16x3 softplus net encodes 6 bands");
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, nullptr, nullptr, nfreq, nullptr, 0, slabs, tiles, n_tiles};
   if (stage == 1) {
     ProfScope prof("sdf_nabla_fwd", (double)P, stream);
@@ -4017,6 +4200,14 @@ int launch_radiance(const RadLayout& L, const void* packed, const float* x, cons
 // per-wave phase totals of the last sdf4_kernel launch (stamps builds only)
 extern "C" int nr_exp_stamps(unsigned long long* out, int n) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(nr::g_nr_stamps), sizeof(unsigned long long) * (size_t)n) == hipSuccess
+             ? nr::kW4 * nr::kStampPh
+             : -1;
+}
+// ... of the last sdf4_kernel launch with STAGE_ = stage (0..4)
+extern "C" int nr_exp_stamps_stage(int stage, unsigned long long* out, int n) {
+  if (stage < 0 || stage > 4 || n > nr::kStampSlot) return -1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(nr::g_nr_stamps), sizeof(unsigned long long) * (size_t)n,
+                             sizeof(unsigned long long) * (size_t)(1 + stage) * nr::kStampSlot) == hipSuccess
              ? nr::kW4 * nr::kStampPh
              : -1;
 }

@@ -13,6 +13,9 @@ from neurecon_amd import build as B  # noqa: E402
 VARIANTS = {
     'base': [],
     'stamps': ['-DNR_EXP_STAMPS'],
+    # every sdf4_kernel instance on one embed_feature / embed_backward call per row (the encoding before Enc4)
+    'rowenc': ['-DNR_EXP_ROW_ENC'],
+    'stamps_rowenc': ['-DNR_EXP_STAMPS', '-DNR_EXP_ROW_ENC'],
 }
 
 

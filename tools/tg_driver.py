@@ -63,9 +63,12 @@ def main():
         if a.stamps:
             fn()
             torch.cuda.synchronize()
-            buf = np.zeros(2048 * 8 * 6, dtype=np.uint64)
+            # values per wave (kStampPh) from the library: the call returns 8 waves x values per wave
+            one = np.zeros(1, dtype=np.uint64)
+            nph = L.lib().nr_exp_stamps(one.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(1)) // 8
+            buf = np.zeros(2048 * 8 * nph, dtype=np.uint64)
             nw = L.lib().nr_exp_stamps(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(buf.size))
-            v = buf.reshape(-1, 6)[:min(P // 128, 256) * 8]
+            v = buf.reshape(-1, nph)[:min(P // 128, 256) * 8, :6]  # (6..: sdf4_kernel's whole-tile phases)
             tot = v.sum(1)
             names = ['VMEM issue', 'MFMA loop', 'bias + wait', 'barrier', 'tile start', 'epilogue VALU']
             order = [4, 0, 1, 2, 5, 3]
