@@ -229,6 +229,13 @@ typedef struct {
    * u = (W0f W8f) h7 + (W0f b8f + b0) in the geometry feature's place and the radiance net's layer 0
    * runs over its small inputs only.  NULL: the feature goes through layer 0 as in the reference. */
   const void* fold_packed;
+  /* Order of a chunk's persistent MLP launches.  0 (default): the mid-point, radiance and compacted
+   * reverse-pass launches claim their 128-point tiles at run time (one atomic per tile), and in the
+   * deferred-nabla render without NeRF++ (calc_normal set) the reverse pass runs on a library-owned side
+   * stream beside the mid-point -> radiance chain, joined before the compositing -- unless `stream` is
+   * being captured into a graph.  != 0: everything on `stream` in one order, tiles at a fixed stride.
+   * The maps are bit-identical either way. */
+  int serial_order;
 } NrNeusArgs;
 
 #define NR_DEFAULT_WORKSPACE_BYTES ((size_t)4 << 30) /* 4 GiB */
@@ -1113,6 +1120,11 @@ int nr_profile_enable(int on);
  * recorded launch costs two event markers (and, for compacted launches, a count copy) on the stream */
 int nr_profile_filter(const char* prefix);
 int nr_profile_read(NrKernelStat* out, int max, int* n_out);
+
+/* Cap on the workgroups of the persistent MLP launches (one workgroup per compute unit by default):
+ * n > 0 launches at most n workgroups, 0 restores the compute-unit count.  Process-wide; results do not
+ * depend on it.  A small cap makes a small input run many tiles per workgroup (tests). */
+int nr_set_workgroup_cap(int n);
 
 #ifdef __cplusplus
 }

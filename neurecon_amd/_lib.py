@@ -57,7 +57,7 @@ class NrNeusArgs(ctypes.Structure):
         ('workspace', _c_p), ('workspace_bytes', _c_sz),
         ('u_rand', _c_p), ('t_out_rand', _c_p), ('s_dev', _c_p), ('sample_only', _c_i), ('d_all_out', _c_p),
         ('no_mid_skip', _c_i), ('no_defer', _c_i), ('max_chunk_rays', _c_i64), ('max_workspace_bytes', _c_sz),
-        ('fold_packed', _c_p),
+        ('fold_packed', _c_p), ('serial_order', _c_i),
     ]
 
 
@@ -317,6 +317,7 @@ _SIGS = {
     'nr_gemm32': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i, _c_p, _c_p, _c_i64, _c_i64, _c_i, _c_i, _c_i, _c_p]),
     'nr_profile_filter': (_c_i, [ctypes.c_char_p]),
     'nr_profile_read': (_c_i, [ctypes.POINTER(NrKernelStat), _c_i, ctypes.POINTER(_c_i)]),
+    'nr_set_workgroup_cap': (_c_i, [_c_i]),
 }
 
 EXPORTED = tuple(_SIGS)
@@ -377,6 +378,11 @@ def profile_read():
     n = ctypes.c_int(0)
     check(lib().nr_profile_read(buf, 64, ctypes.byref(n)))
     return {buf[i].name.decode(): (buf[i].launches, buf[i].ms, buf[i].units) for i in range(n.value)}
+
+
+def set_workgroup_cap(n):
+    """at most n workgroups per persistent MLP launch; 0: one per compute unit (the default)"""
+    check(lib().nr_set_workgroup_cap(int(n)))
 
 
 _WS = {}

@@ -206,6 +206,12 @@ __attribute__((used)) static const char kBuildIdMarker[] = "NR_BUILD_ID=" NR_BUI
 const char* nr_build_id(void) { return kBuildIdMarker + 12; }
 const char* nr_last_error(void) { return g_err.c_str(); }
 
+int nr_set_workgroup_cap(int n) {
+  NR_REQUIRE(n >= 0, NR_ERR_ARG, "nr_set_workgroup_cap: the cap must be >= 0");
+  set_workgroup_cap(n);
+  return NR_OK;
+}
+
 size_t nr_sdf_packed_bytes(const NrSdfDesc* d) {
   if (check_sdf_desc(d)) return 0;
   return sdf_layout(*d).total;

@@ -132,20 +132,29 @@ int launch_pack_vec(const float* src, int off, int nvalid, int n, char* dst, hip
 int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
                float* feature, int nfreq, void* ws, size_t ws_bytes, hipStream_t stream,
                const int* P_dev = nullptr, int P_mult = 0,  // P_dev: device count, P_eff = min(P, *P_dev * P_mult)
-               const void* f8_alt = nullptr);  // f16x3 softplus net: a packed op run in F8's place (fold_layout's F8')
+               const void* f8_alt = nullptr,  // f16x3 softplus net: a packed op run in F8's place (fold_layout's F8')
+               int* claim = nullptr);  // tile claims (below): honoured by the f16x3 nabla + feature launch
 // deferred sample nablas (sdf4_kernel STAGE 1 / 2): stage 1 = sdf + slabs per 16-point tile into
 // `slabs` (P/16 x kSlabColBytes); stage 2 = nablas of the tiles tiles[0 .. *n_tiles) from their slabs;
 // stage 4 = nablas of the points tiles[0 .. *n_tiles) (neus_point_list's layout: 16-aligned segments of
 // slots within one 1024-slot range, padded with -1)
 int launch_sdf_deferred(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
-                        int nfreq, float4* slabs, const int* tiles, const int* n_tiles, int stage, hipStream_t stream);
+                        int nfreq, float4* slabs, const int* tiles, const int* n_tiles, int stage, hipStream_t stream,
+                        int* claim = nullptr);  // tile claims (below): honoured by stages 2 and 4
 int launch_nerf(const NerfLayout& L, const void* packed, const float* x4, const float* vdir, int64_t vdiv,
                 int64_t vmod, int64_t P, float* sigma, float* rgb, hipStream_t stream,
                 const int* P_dev = nullptr);  // P_dev: device count, P_eff = min(P, *P_dev)
 int launch_radiance(const RadLayout& L, const void* packed, const float* x, const float* vdir, int64_t vdiv,
                     int64_t vmod, const float* normals, const float* feature, int64_t P, float* rgb, int nfreq_view,
                     hipStream_t stream, const int* P_dev = nullptr,  // P_dev: device count, P_eff = min(P, *P_dev)
-                    const void* r0_fold = nullptr);  // rad4_kernel case: `feature` holds u, layer 0 runs fold_layout's R0'
+                    const void* r0_fold = nullptr,  // rad4_kernel case: `feature` holds u, layer 0 runs fold_layout's R0'
+                    int* claim = nullptr);  // tile claims (below): honoured by rad4_kernel
+// Tile claims: `claim` points to a device int that is 0 when the launch starts.  A workgroup's first tile is
+// its block index; it takes every later one as gridDim.x + atomicAdd(claim, 1), so a workgroup that
+// finishes early (or starts late, beside another stream's kernel) runs the tiles that are left instead of a
+// fixed share.  nullptr: tiles at the fixed stride gridDim.x.  Results do not depend on it.
+// set_workgroup_cap: at most n workgroups per persistent MLP launch (0: one per compute unit).
+void set_workgroup_cap(int n);
 
 // NeuS fold pack (nr_neus_fold_pack): the SDF net's feature layer folded into the radiance net's
 // layer 0.  F8' (KB 16, NBO 16: h7 -> u = U h7 + bu) runs in F8's place in sdf4_kernel; R0' (KB kbs,

@@ -17,6 +17,7 @@
 //  * Everything per point (embedding, nabla chain rule through sin/cos, sdf row dot product,
 //    sigmoid head) is VALU work in the same kernel.
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include "nr_common.h"
 #include "nr_mlp.h"
@@ -689,6 +690,11 @@ struct SdfKArgs {
   const int* tiles;   // STAGE 2: 16-point tiles to run the reverse pass on
   const int* n_tiles; //   ... and their count (device)
   const char* f8_alt; // sdf4_kernel: a packed op to run in F8's place (the NeuS fold's F8', nr_neus_fold_pack), or null
+};
+// ... of the sdf4_kernel instances that can claim their tiles (kSdfClaim): the others keep SdfKArgs, and with
+// it their kernel arguments' layout and their instructions
+struct SdfKArgsC : SdfKArgs {
+  int* claim;  // tile claim counter (nr_mlp.h), or null
 };
 
 template <int P, bool NABLA>
@@ -1634,10 +1640,15 @@ struct NoPre4 {
 // pair (NABLA, no feature): STAGE 1 runs the forward and leaves each 16-point tile's slabs (softplus
 // log2 terms, d sdf / d z7) in a.slabs at the tile's index; STAGE 2 runs only the reverse pass, on the
 // 16-point tiles of the device list a.tiles[0 .. *a.n_tiles) (nablas of those points).
+// tile claims (nr_mlp.h, SdfKArgsC::claim): the instances that run behind a render's sampling -- the mid-point
+// launch and the reverse-only launches
+template <bool NABLA, bool FEAT, int STAGE_>
+constexpr bool kSdfClaim = NABLA && (STAGE_ == 2 || STAGE_ == 4 || (FEAT && STAGE_ == 0));
+
 template <bool NABLA, bool FEAT, int STAGE_>
 __global__ __attribute__((amdgpu_flat_work_group_size(STAGE_ == 3 ? 256 : kT4, STAGE_ == 3 ? 256 : kT4),
                           amdgpu_waves_per_eu(kWPE, kWPE)))
-void sdf4_kernel(SdfKArgs a) {
+void sdf4_kernel(std::conditional_t<kSdfClaim<NABLA, FEAT, STAGE_>, SdfKArgsC, SdfKArgs> a) {
   // STAGE_ 3: the forward of a small launch (launch_sdf: at most 64 points per CU) on 64-point tiles of 4
   // waves, one per SIMD -- twice the CUs of 128-point tiles, half the matrix work per CU and chunk (each
   // workgroup streams the whole net once per tile either way); otherwise STAGE 0, the same per-point code
@@ -1645,6 +1656,7 @@ void sdf4_kernel(SdfKArgs a) {
   // lane reading its point's slab codes from that point's own tile)
   constexpr int STAGE = STAGE_ == 3 ? 0 : (STAGE_ == 4 ? 2 : STAGE_);
   constexpr bool COMPACT = STAGE_ == 4;
+  constexpr bool CLAIM = kSdfClaim<NABLA, FEAT, STAGE_>;  // the others keep the fixed stride and their instructions
   constexpr int NW = STAGE_ == 3 ? 4 : kW4;  // waves per workgroup
   static_assert(STAGE_ != 3 || (!NABLA && !FEAT), "narrow tiles: forward-only launches");
   static_assert(STAGE == 0 || (NABLA && !FEAT), "deferred nablas: no feature");
@@ -1671,8 +1683,8 @@ void sdf4_kernel(SdfKArgs a) {
   constexpr bool TABF = !SLABS;
   constexpr int FM = TABF ? kTab : kSlot;  // mode of the forward ops
   constexpr int LDSB = RING * CB + (SLABS ? kSlabRing * kSlab4 : 0) + (TABF ? 2 * kTabBytes : 0);
-  __shared__ __attribute__((aligned(16))) char smem[LDSB];
-  static_assert(LDSB <= 160 * 1024, "LDS budget");
+  __shared__ __attribute__((aligned(16))) char smem[LDSB + (CLAIM ? 16 : 0)];  // CLAIM: the claimed tile index
+  static_assert(LDSB + (CLAIM ? 16 : 0) <= 160 * 1024, "LDS budget");
   static_assert(!TABF || RING * CB + 2 * kTabBytes == LDSB, "the bias table follows the weight ring");
   WStream4<CB, RING, NW> ws{smem, SLABS ? smem + RING * CB : nullptr, 0, 0, 0, 0, TABF ? smem + RING * CB : nullptr, 0};
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1723,8 +1735,18 @@ void sdf4_kernel(SdfKArgs a) {
   const int64_t Pn = COMPACT      ? ((int64_t)(*a.n_tiles) + 15) / 16 * 16
                      : STAGE == 2 ? (int64_t)(*a.n_tiles) * kPointsPerWG / kW4
                                   : (a.P_dev ? min(a.P, (int64_t)(*a.P_dev) * a.P_mult) : a.P);
-  for (int64_t base = (int64_t)blockIdx.x * PPW; base < Pn; base += (int64_t)gridDim.x * PPW) {
-    const bool has_next = base + (int64_t)gridDim.x * PPW < Pn;
+  // Claimed tiles: thread 0 draws the next tile's index at the tile start, ahead of the point loads (whose
+  // wait then covers the atomic's return), and leaves it in LDS; every wave reads it before the tile's last
+  // op, which needs has_next -- the chunk barriers of the ops between order the write before those reads,
+  // the last op's barriers order the reads before the next tile's write.
+  int* claim = nullptr;  // the counter; stays null in the instances that cannot claim (no new code there)
+  if constexpr (CLAIM) claim = a.claim;
+  int* const claim_lds = (int*)(smem + LDSB);
+  int64_t next = 0;  // the next tile's first point (claimed)
+  for (int64_t base = (int64_t)blockIdx.x * PPW; base < Pn; base = claim ? next : base + (int64_t)gridDim.x * PPW) {
+    bool has_next = base + (int64_t)gridDim.x * PPW < Pn;
+    int claimed = 0;
+    if (claim && threadIdx.x == 0) claimed = atomicAdd(claim, 1);
     NR_STAMP_VAR(ts0);
     NR_STAMP_VAR(ts1);  // the first op starts
     NR_STAMP_VAR(te0);  // the last op has returned
@@ -1773,6 +1795,7 @@ void sdf4_kernel(SdfKArgs a) {
       xs[q][1] = a.pts[pq[q] * 3 + 1];
       xs[q][2] = a.pts[pq[q] * 3 + 2];
     }
+    if (claim && threadIdx.x == 0) *claim_lds = claimed;
     float4 E[kNC][4];
     float mE[kNC], xinv[kNC];
     f16x8 Uh[kNC][12], Ul[kNC][12], Vh[kNC][12], Vl[kNC][12];
@@ -2057,6 +2080,10 @@ void sdf4_kernel(SdfKArgs a) {
       bwd(I14{}, I16{}, I16{}, IC16{}, LeanNext{}, B3, OP(B2), Uh, Ul, Vh, Vl, 2, 0, 1);
       bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B2, OP(B1), Vh, Vl, Uh, Ul, 1, 0, 0);
       bwd(I16{}, I16{}, I16{}, IC16{}, LeanNext{}, B1, OP(B0), Uh, Ul, Vh, Vl, 0, 0, -1);
+      if (claim) {
+        next = (int64_t)(gridDim.x + __builtin_amdgcn_readfirstlane(*claim_lds)) * PPW;
+        has_next = next < Pn;
+      }
       if constexpr (STAGE == 2) bwd(I16{}, I4{}, I0{}, IC16{}, LeanNext{}, B0, has_next ? OP(B7) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
       else bwd(I16{}, I4{}, I0{}, IC4{}, SlotNext{}, B0, has_next ? OP(F0) : nullptr, Vh, Vl, Uh, Ul, 0, 4, -1);
       NR_STAMP_SET(te0);
@@ -2245,6 +2272,10 @@ struct RadKArgs {
   int nfreq_view;  // <0: identity
   const int* P_dev;  // optional device count: the first min(P, *P_dev) points are evaluated
   const char* r0_fold;  // rad4_kernel<KBS, true>: the fold pack's R0' (then `feature` holds u), or null
+};
+// ... of rad4_kernel<KBS, true>, the render's instances, which can claim their tiles
+struct RadKArgsC : RadKArgs {
+  int* claim;  // tile claim counter (nr_mlp.h), or null
 };
 
 // small input features [x(3), view-embedding(3+6F or 3), normals(3)] in block layout ([x(3)] only
@@ -2531,15 +2562,17 @@ struct FoldEpi4 {
 
 template <int KBS, bool FOLD>
 __global__ __attribute__((amdgpu_flat_work_group_size(kT4, kT4), amdgpu_waves_per_eu(kWPE, kWPE)))
-void rad4_kernel(RadKArgs a) {
+void rad4_kernel(std::conditional_t<FOLD, RadKArgsC, RadKArgs> a) {
   constexpr int KF = FOLD ? 0 : 16;  // op 0's input blocks: feature (16 unless folded), then the small inputs
   constexpr int K0 = KF + KBS;
   constexpr int C0 = chunk_bytes(K0), C16 = chunk_bytes(16);
   constexpr int CM = C0 > C16 ? C0 : C16;  // the ring's slot
-  __shared__ __attribute__((aligned(16))) char smem[kRing * CM + (3 * 256 + 4) * 4];
-  static_assert(kRing * CM + (3 * 256 + 4) * 4 <= 160 * 1024, "LDS budget");
+  constexpr bool CLAIM = FOLD;  // tile claims (nr_mlp.h, a.claim): the render instances; the others keep their code
+  __shared__ __attribute__((aligned(16))) char smem[kRing * CM + (3 * 256 + 4) * 4 + (CLAIM ? 16 : 0)];
+  static_assert(kRing * CM + (3 * 256 + 4) * 4 + (CLAIM ? 16 : 0) <= 160 * 1024, "LDS budget");
   WStream4<CM> ws{smem, nullptr, 0, 0, 0};
   float* head = (float*)(smem + kRing * CM);  // [3][256] weights, then [3] bias
+  int* const claim_lds = (int*)(head + 3 * 256 + 4);  // the claimed tile index (a.claim, as in sdf4_kernel)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = lane & 15, g = lane >> 4;
   const RadLayout& L = a.L;
@@ -2558,8 +2591,16 @@ void rad4_kernel(RadKArgs a) {
   Pend4 pd{};
   NoPre4 nopre;
   const int64_t Pn = a.P_dev ? min(a.P, (int64_t)*a.P_dev) : a.P;
-  for (int64_t base = (int64_t)blockIdx.x * kPointsPerWG; base < Pn; base += (int64_t)gridDim.x * kPointsPerWG) {
-    const bool has_next = base + (int64_t)gridDim.x * kPointsPerWG < Pn;
+  int* claim = nullptr;  // the counter; stays null in the instances that cannot claim (no new code there)
+  if constexpr (CLAIM) claim = a.claim;
+  int64_t next = 0;  // the next tile's first point (claimed)
+  for (int64_t base = (int64_t)blockIdx.x * kPointsPerWG; base < Pn;
+       base = claim ? next : base + (int64_t)gridDim.x * kPointsPerWG) {
+    bool has_next = base + (int64_t)gridDim.x * kPointsPerWG < Pn;
+    // thread 0 draws the next tile ahead of the point loads and leaves it in LDS behind them; every wave
+    // reads it before the last op, with the three ops' chunk barriers in between
+    int claimed = 0;
+    if (claim && threadIdx.x == 0) claimed = atomicAdd(claim, 1);
     const int64_t p0 = base + wave * 16 * kNC;
     f16x8 Uh[kNC][12], Ul[kNC][12], Vh[kNC][12], Vl[kNC][12];
     float m_in[kNC], xinv[kNC], mrun[kNC];
@@ -2614,6 +2655,7 @@ void rad4_kernel(RadKArgs a) {
       xinv[q] = 1.0f / s;
       mrun[q] = 0.0f;
     }
+    if (claim && threadIdx.x == 0) *claim_lds = claimed;
     auto next_scales = [&](int kb, float (&sc)[kNC]) {
       const float4 v = ws.buf()[2 * kb * 64 + 8];
 #pragma unroll
@@ -2656,6 +2698,10 @@ void rad4_kernel(RadKArgs a) {
     float part[kNC][3];
 #pragma unroll
     for (int q = 0; q < kNC; ++q) part[q][0] = part[q][1] = part[q][2] = 0.0f;
+    if (claim) {
+      next = (int64_t)(gridDim.x + __builtin_amdgcn_readfirstlane(*claim_lds)) * kPointsPerWG;
+      has_next = next < Pn;
+    }
     op4<16, 16, C0, false, false>(ws, OP(3), has_next ? OP(0) : nullptr, Vh, Vl, xinv, pd, nopre,
                                   HeadEpi4{head, part, g}, lane);
 #pragma unroll
@@ -4002,15 +4048,18 @@ static int cu_count() {
   return cus;
 }
 
+static std::atomic<int> g_wg_cap{0};
+void set_workgroup_cap(int n) { g_wg_cap = n; }
+
 static int grid_for(int64_t P, int ppw = kPointsPerWG) {
-  const int cus = cu_count();
+  const int cap = g_wg_cap.load(), cus = cap > 0 ? std::min(cap, cu_count()) : cu_count();
   const int64_t need = (P + ppw - 1) / ppw;
   return (int)(need < cus ? (need > 0 ? need : 1) : cus);
 }
 
 int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
                float* feature, int nfreq, void* ws, size_t ws_bytes, hipStream_t stream, const int* P_dev,
-               int P_mult, const void* f8_alt) {
+               int P_mult, const void* f8_alt, int* claim) {
   if (P <= 0) return NR_OK;
   const int grid = grid_for(P);
   NR_REQUIRE(!f8_alt || (feature && L.prec == NR_PREC_F16X3 && !L.siren), NR_ERR_ARG,
@@ -4019,6 +4068,7 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
              "sdf: the f16x3 softplus net encodes 6 bands");
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, feature, (float4*)ws, nfreq, P_dev, P_mult, nullptr, nullptr,
              nullptr, (const char*)f8_alt};
+  const SdfKArgsC ac{a, claim};  // the instances that claim their tiles (kSdfClaim)
   ProfScope prof(nabla ? (feature ? "sdf_nabla_feat" : "sdf_nabla") : (feature ? "sdf_feat" : "sdf_fwd"), (double)P,
                  stream, P_dev, P_mult);
   if (L.siren) {
@@ -4040,7 +4090,7 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
     const size_t need = (size_t)grid * kScratchPerWG;
     NR_REQUIRE(ws && ws_bytes >= need, NR_ERR_WORKSPACE, "sdf nabla workspace too small");
     if (L.prec == NR_PREC_F16X3) {
-      if (feature) hipLaunchKernelGGL((sdf4_kernel<true, true, 0>), dim3(grid), dim3(kT4), 0, stream, a);
+      if (feature) hipLaunchKernelGGL((sdf4_kernel<true, true, 0>), dim3(grid), dim3(kT4), 0, stream, ac);
       else hipLaunchKernelGGL((sdf4_kernel<true, false, 0>), dim3(grid), dim3(kT4), 0, stream, a);
     }
     else hipLaunchKernelGGL((sdf_kernel<NR_PREC_FP32, true>), dim3(grid), dim3(kThreads), 0, stream, a);
@@ -4058,21 +4108,23 @@ int launch_sdf(const SdfLayout& L, const void* packed, const float* pts, int64_t
 }
 
 int launch_sdf_deferred(const SdfLayout& L, const void* packed, const float* pts, int64_t P, float* sdf, float* nabla,
-                        int nfreq, float4* slabs, const int* tiles, const int* n_tiles, int stage, hipStream_t stream) {
+                        int nfreq, float4* slabs, const int* tiles, const int* n_tiles, int stage, hipStream_t stream,
+                        int* claim) {
   if (P <= 0) return NR_OK;
   NR_REQUIRE(L.prec == NR_PREC_F16X3 && !L.siren, NR_ERR_UNSUPPORTED, "deferred nablas: f16x3 softplus nets");
   NR_REQUIRE(nfreq == kEncBands, NR_ERR_UNSUPPORTED, "sdf: the f16x3 softplus net encodes 6 bands");
   SdfKArgs a{(const char*)packed, L, pts, P, sdf, nabla, nullptr, nullptr, nfreq, nullptr, 0, slabs, tiles, n_tiles};
+  const SdfKArgsC ac{a, claim};  // stages 2 and 4 claim their tiles (kSdfClaim)
   if (stage == 1) {
     ProfScope prof("sdf_nabla_fwd", (double)P, stream);
     hipLaunchKernelGGL((sdf4_kernel<true, false, 1>), dim3(grid_for(P)), dim3(kT4), 0, stream, a);
   } else if (stage == 2) {
     ProfScope prof("sdf_nabla_bwd", (double)P, stream, n_tiles, 16);
-    hipLaunchKernelGGL((sdf4_kernel<true, false, 2>), dim3(grid_for(P)), dim3(kT4), 0, stream, a);
+    hipLaunchKernelGGL((sdf4_kernel<true, false, 2>), dim3(grid_for(P)), dim3(kT4), 0, stream, ac);
   } else {  // 4: `tiles` lists sample slots (neus_point_list); the units count its padding too
     NR_REQUIRE(stage == 4, NR_ERR_ARG, "deferred nablas: bad stage");
     ProfScope prof("sdf_nabla_bwd", (double)P, stream, n_tiles, 1);
-    hipLaunchKernelGGL((sdf4_kernel<true, false, 4>), dim3(grid_for(P)), dim3(kT4), 0, stream, a);
+    hipLaunchKernelGGL((sdf4_kernel<true, false, 4>), dim3(grid_for(P)), dim3(kT4), 0, stream, ac);
   }
   NR_HIP_CHECK(hipGetLastError());
   return NR_OK;
@@ -4153,13 +4205,14 @@ int launch_radiance_train32(const RadLayout& L, const void* packed, const float*
 
 int launch_radiance(const RadLayout& L, const void* packed, const float* x, const float* vdir, int64_t vdiv,
                     int64_t vmod, const float* normals, const float* feature, int64_t P, float* rgb, int nfreq_view,
-                    hipStream_t stream, const int* P_dev, const void* r0_fold) {
+                    hipStream_t stream, const int* P_dev, const void* r0_fold, int* claim) {
   if (P <= 0) return NR_OK;
   const int grid = grid_for(P);
   NR_REQUIRE(!r0_fold || (L.prec == NR_PREC_F16X3 && !L.siren && L.D == 4), NR_ERR_ARG,
              "radiance: the folded layer 0 needs the f16x3 ReLU D=4 net");
   RadKArgs a{(const char*)packed, L, x, vdir, vdiv, vmod, normals, feature, P, rgb, nfreq_view, P_dev,
              (const char*)r0_fold};
+  const RadKArgsC ac{a, claim};  // rad4_kernel<KBS, true>
   ProfScope prof("radiance", (double)P, stream, P_dev, 1);
   const bool h3 = L.prec == NR_PREC_F16X3;
   // (small-input blocks, activation, depth) variants
@@ -4176,8 +4229,8 @@ int launch_radiance(const RadLayout& L, const void* packed, const float* x, cons
   }
   if (h3 && !L.siren && L.D == 4) {  // the v3 pipeline (rad4_kernel)
     if (r0_fold) {
-      if (L.kbs == 2) hipLaunchKernelGGL((rad4_kernel<2, true>), dim3(grid), dim3(kT4), 0, stream, a);
-      else hipLaunchKernelGGL((rad4_kernel<4, true>), dim3(grid), dim3(kT4), 0, stream, a);
+      if (L.kbs == 2) hipLaunchKernelGGL((rad4_kernel<2, true>), dim3(grid), dim3(kT4), 0, stream, ac);
+      else hipLaunchKernelGGL((rad4_kernel<4, true>), dim3(grid), dim3(kT4), 0, stream, ac);
     } else if (L.kbs == 2) hipLaunchKernelGGL((rad4_kernel<2, false>), dim3(grid), dim3(kT4), 0, stream, a);
     else hipLaunchKernelGGL((rad4_kernel<4, false>), dim3(grid), dim3(kT4), 0, stream, a);
   } else if (!L.siren && L.D == 4) {

@@ -7,6 +7,7 @@
 // (acc_type<float, is_cuda=false> = double), each prefix rounded to fp32.
 #include <algorithm>
 #include <cstdint>
+#include <mutex>
 
 #include "nr_common.h"
 #include "nr_mlp.h"
@@ -1086,7 +1087,7 @@ static size_t neus_bind(const NrNeusArgs& a, int64_t Rc, char* base, NeusChunk& 
   h.midc = cv.take(Mm * 3);
   h.mvd = cv.take(Mm * 3);
   h.mrad = cv.take(Mm * 3);
-  h.mcnt = cv.take<int>(1);
+  h.mcnt = cv.take<int>(3);  // the count, then the mid-point and radiance launches' tile claims (one memset)
   c.pts_nog = cv.take(std::max<size_t>(n_nog, 1) * Rc * 3);
   c.s_nog = cv.take(std::max<size_t>(n_nog, 1) * Rc);
   c.idv = cv.take<int>(S * Rc);
@@ -1114,10 +1115,69 @@ static size_t neus_bind(const NrNeusArgs& a, int64_t Rc, char* base, NeusChunk& 
   // flags per sample slot; the list (neus_point_list) pads each 1024-slot segment to 16 entries
   c.tflag = cv.take<int>(slots);
   c.tiles = cv.take<int>(slots + 16 * ((slots + 1023) / 1024));
-  c.tcnt = cv.take<int>(1);
+  c.tcnt = cv.take<int>(2);  // the list's length, then the reverse pass's tile claims (one memset)
   h.mlp_ws = base ? base + cv.off : nullptr;
   h.mlp_bytes = base ? a.workspace_bytes - cv.off : 0;
   return cv.off + nr_mlp_workspace_bytes(1);
+}
+
+// The side stream of the two-branch chunk (neus_chunk): one per device, non-blocking, created at its first
+// use and kept for the life of the process, with the two events of its fork and join.
+struct SideStream {
+  hipStream_t s = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+constexpr int kMaxSideDev = 64;
+static std::mutex g_side_mu;
+static SideStream g_side[kMaxSideDev];
+
+static int side_stream(SideStream& out) {
+  int dev = 0;
+  NR_HIP_CHECK(hipGetDevice(&dev));
+  NR_REQUIRE(dev >= 0 && dev < kMaxSideDev, NR_ERR_UNSUPPORTED, "nr_neus_render: device index beyond the side streams");
+  std::lock_guard<std::mutex> lk(g_side_mu);
+  SideStream& g = g_side[dev];
+  if (!g.s) {
+    SideStream n;
+    NR_HIP_CHECK(hipStreamCreateWithFlags(&n.s, hipStreamNonBlocking));
+    NR_HIP_CHECK(hipEventCreateWithFlags(&n.fork, hipEventDisableTiming));
+    NR_HIP_CHECK(hipEventCreateWithFlags(&n.join, hipEventDisableTiming));
+    g = n;
+  }
+  out = g;
+  return NR_OK;
+}
+
+// `to` waits for what `from` holds now.  The record and the wait are one step under the lock: two host
+// threads rendering on one device share the events, and a wait must see its own thread's record.
+static int stream_after(hipStream_t to, hipStream_t from, hipEvent_t ev) {
+  std::lock_guard<std::mutex> lk(g_side_mu);
+  NR_HIP_CHECK(hipEventRecord(ev, from));
+  NR_HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
+  return NR_OK;
+}
+
+// A fork that always joins: a chunk that fails between the two still leaves `st` ordered after the side
+// stream's work on its workspace.
+struct SideJoin {
+  hipStream_t st;
+  SideStream side;
+  bool open = false;
+  int join() {
+    if (!open) return NR_OK;
+    open = false;
+    return stream_after(st, side.s, side.join);
+  }
+  ~SideJoin() { (void)join(); }
+};
+
+static bool stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {  // e.g. the legacy stream beside a capture: stay in order
+    (void)hipGetLastError();
+    return true;
+  }
+  return cs != hipStreamCaptureStatusNone;
 }
 
 static int neus_chunk(const NrNeusArgs& a, NeusChunk c, const NeusHost& h, int64_t ray0, int R, hipStream_t st) {
@@ -1211,21 +1271,37 @@ static int neus_chunk(const NrNeusArgs& a, NeusChunk c, const NeusHost& h, int64
     if ((rc = sample_sdf(cu.pts, (int64_t)n_up * R, c.snew, slot0))) return rc;
   }
   if (c.n_iters > 0 && (rc = merge(c.S - n_up))) return rc;
+  // Tile claims (nr_mlp.h) of the three persistent launches behind the sampling, unless the caller asked for
+  // the serial order: the counters share the memsets of the counts they follow (neus_bind).
+  const bool claims = !a.serial_order;
+  // Two branches (deferred nablas, no NeRF++): the sample nablas -- flags, list, compacted reverse pass, all
+  // writing nraw / tflag / tiles / tcnt alone -- run on the side stream beside the mid-point -> radiance chain
+  // on st, which reads none of them; st joins before neus_gather_nablas.  With claimed tiles the reverse
+  // pass's workgroups take the compute units that the other branch's last round leaves idle.  A stream
+  // under capture keeps the one-stream order.
+  const bool two = defer && claims && a.calc_normal && a.N_outside == 0 && !stream_capturing(st);
+  SideJoin sj{st};
   if (defer) {  // nablas of the tiles holding a sample of non-zero interval weight; the rest stay 0
     const int64_t nslot = (int64_t)c.S * R;
     c.tshift = 0;  // flags per sample slot, the reverse pass on the listed samples (sdf4_kernel STAGE 4)
-    NR_HIP_CHECK(hipMemsetAsync(c.nraw, 0, (size_t)nslot * 3 * sizeof(float), st));
+    hipStream_t sr = st;  // the stream of the sample nablas
+    if (two) {
+      if ((rc = side_stream(sj.side)) || (rc = stream_after(sj.side.s, st, sj.side.fork))) return rc;
+      sj.open = true;
+      sr = sj.side.s;
+    }
+    NR_HIP_CHECK(hipMemsetAsync(c.nraw, 0, (size_t)nslot * 3 * sizeof(float), sr));
     if (a.calc_normal && a.N_outside == 0) {  // normals_volume is the only reader of the sample nablas here
       // (with NeRF++ the flags need the background's alphas: after the background net, below)
-      NR_HIP_CHECK(hipMemsetAsync(c.tflag, 0, (size_t)nslot * sizeof(int), st));
-      NR_HIP_CHECK(hipMemsetAsync(c.tcnt, 0, sizeof(int), st));
+      NR_HIP_CHECK(hipMemsetAsync(c.tflag, 0, (size_t)nslot * sizeof(int), sr));
+      NR_HIP_CHECK(hipMemsetAsync(c.tcnt, 0, (claims ? 2 : 1) * sizeof(int), sr));
       const int64_t nq = (int64_t)(c.S - 1) * R;
-      hipLaunchKernelGGL(neus_sample_need, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, c, a.s_dev, a.s);
+      hipLaunchKernelGGL(neus_sample_need, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, sr, c, a.s_dev, a.s);
       NR_HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(neus_point_list, dim3((unsigned)((nslot + 1023) / 1024)), dim3(1024), 0, st, c, nslot);
+      hipLaunchKernelGGL(neus_point_list, dim3((unsigned)((nslot + 1023) / 1024)), dim3(1024), 0, sr, c, nslot);
       NR_HIP_CHECK(hipGetLastError());
       if ((rc = launch_sdf_deferred(SL, a.sdf_packed, c.pts, nslot, nullptr, c.nraw, a.sdf->multires, c.slabs, c.tiles,
-                                    c.tcnt, 4, st)))
+                                    c.tcnt, 4, sr, claims ? c.tcnt + 1 : nullptr)))
         return rc;
     }
   }
@@ -1238,7 +1314,7 @@ static int neus_chunk(const NrNeusArgs& a, NeusChunk c, const NeusHost& h, int64
   {
     ProfScope prof("neus_points", (double)R, st);
     hipLaunchKernelGGL(neus_expand, dim3((unsigned)(((int64_t)c.S * R + 255) / 256)), dim3(256), 0, st, c,
-                       (int)!(defer && a.N_outside > 0));
+                       (int)!(defer && (a.N_outside > 0 || two)));
   }
   NR_HIP_CHECK(hipGetLastError());
   // SDF + nablas at the samples (neus.py:294); already in sv / nv on the fused path
@@ -1255,26 +1331,34 @@ static int neus_chunk(const NrNeusArgs& a, NeusChunk c, const NeusHost& h, int64
     f8p = (const char*)a.fold_packed + FL.f8_off;
     r0p = (const char*)a.fold_packed + FL.r0_off;
   }
+  int* const claim_mid = claims ? h.mcnt + 1 : nullptr;
+  int* const claim_rad = claims ? h.mcnt + 2 : nullptr;
   if (a.radiance_out || a.no_mid_skip) {  // every mid-point, as the reference
+    if (claims) NR_HIP_CHECK(hipMemsetAsync(h.mcnt, 0, 3 * sizeof(int), st));
     if ((rc = launch_sdf(SL, a.sdf_packed, c.mids, Pm, c.sdf_m, c.nab_m, c.feat_m, a.sdf->multires, mlp_ws, mlp_bytes,
-                         st, nullptr, 0, f8p)))
+                         st, nullptr, 0, f8p, claim_mid)))
       return rc;
     if ((rc = launch_radiance(RL, a.rad_packed, c.mids, c.rd, 1, R, c.nab_m, c.feat_m, Pm, c.rad_m,
-                              a.rad->multires_view, st, nullptr, r0p)))
+                              a.rad->multires_view, st, nullptr, r0p, claim_rad)))
       return rc;
   } else {  // only the mid-points whose alpha is not exactly 0 (neus_mid_compact); bit-identical maps
-    NR_HIP_CHECK(hipMemsetAsync(h.mcnt, 0, sizeof(int), st));
+    NR_HIP_CHECK(hipMemsetAsync(h.mcnt, 0, (claims ? 3 : 1) * sizeof(int), st));
     const dim3 g1((unsigned)((Pm + 255) / 256));
     hipLaunchKernelGGL(neus_mid_compact, dim3((unsigned)((Pm + 1023) / 1024)), dim3(1024), 0, st, c, a.s_dev, a.s,
                        h.mcnt, h.mslot, h.midc, h.mvd);
     NR_HIP_CHECK(hipGetLastError());
     if ((rc = launch_sdf(SL, a.sdf_packed, h.midc, Pm, c.sdf_m, c.nab_m, c.feat_m, a.sdf->multires, mlp_ws, mlp_bytes,
-                         st, h.mcnt, 1, f8p)))
+                         st, h.mcnt, 1, f8p, claim_mid)))
       return rc;
     if ((rc = launch_radiance(RL, a.rad_packed, h.midc, h.mvd, 1, INT64_MAX, c.nab_m, c.feat_m, Pm, h.mrad,
-                              a.rad->multires_view, st, h.mcnt, r0p)))
+                              a.rad->multires_view, st, h.mcnt, r0p, claim_rad)))
       return rc;
     hipLaunchKernelGGL(neus_mid_scatter, g1, dim3(256), 0, st, h.mslot, h.mrad, Pm, c.rad_m);
+    NR_HIP_CHECK(hipGetLastError());
+  }
+  if (two) {  // join: the sample nablas are complete; into sorted order (neus_expand left them out)
+    if ((rc = sj.join())) return rc;
+    hipLaunchKernelGGL(neus_gather_nablas, dim3((unsigned)(((int64_t)c.S * R + 255) / 256)), dim3(256), 0, st, c);
     NR_HIP_CHECK(hipGetLastError());
   }
   NeusOut o{ray0, a.rgb, a.depth, a.acc, a.normals, a.d_final, a.sdf_out, a.nablas_out,

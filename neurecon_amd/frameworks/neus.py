@@ -127,7 +127,7 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
                   fixed_s_recp=1 / 64., N_samples=64, N_importance=64, N_outside=0,
                   upsample_algo='official_solution', N_nograd_samples=2048, N_upsample_iters=4,
                   skip_zero_alpha=True, defer_sample_nablas=True, max_workspace_gb=None, fold_feature=True,
-                  **dummy_kwargs):
+                  serial_order=False, **dummy_kwargs):
     """neus.py:118-397, render mode.  skip_zero_alpha (not a reference argument): mid-points whose alpha
     is exactly 0 (and, with NeRF++, the ones outside the bounding sphere) skip the SDF + radiance nets
     when the radiance output is not asked for -- their weight is an exact 0 (or their colour is the
@@ -143,7 +143,10 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
     net, else without effect): the geometry-feature layer, which has no activation, is folded into the
     radiance net's layer 0 once per weight version (RadianceNet.nr_fold_packed), so the mid-points skip one
     256x256 layer product; sampling, sdf, nablas and weights are bit-identical, radiance differs by layer
-    0's rounding.  False: the feature goes through layer 0 as in the reference.
+    0's rounding.  False: the feature goes through layer 0 as in the reference.  serial_order (not a
+    reference argument): True keeps every launch of a chunk on the current stream with tiles at a fixed
+    stride; by default the mid-point, radiance and compacted reverse-pass launches claim their tiles at run
+    time and the reverse pass runs on the library's side stream beside the other two -- bit-identical maps.
     rays_o/rays_d: [(B,) N_rays, 3]; rays_d need not be normalized.
     perturb=True draws the reference's uniforms (same generators, shapes and order) and hands them
     to the kernels."""
@@ -174,6 +177,7 @@ def volume_render(rays_o, rays_d, model, obj_bounding_radius=1.0, batched=False,
     a.s, a.s_dev = 0.0, L.ptr(s_dev)
     a.no_mid_skip = 0 if skip_zero_alpha else 1
     a.no_defer = 0 if defer_sample_nablas else 1
+    a.serial_order = 1 if serial_order else 0
     a.calc_normal, a.white_bkgd = int(bool(calc_normal)), int(bool(white_bkgd))
     if N_outside > 0:
         if not hasattr(model, 'nerf_outside'):
