@@ -548,6 +548,50 @@ int nr_mesh_filter_emit(const int32_t* faces, int64_t F, int64_t V, const uint8_
                         int32_t* faces_out, int64_t faces_cap, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh simplification on the device (nr_meshsimplify.hip): vertex clustering, the decimation users of
+ * extract_mesh's PLY run in MeshLab or Open3D (simplify_vertex_clustering) before they ship or view it.
+ * All vertices in one cell of a uniform grid of cell size h become one vertex; faces whose vertices no
+ * longer lie in three different cells, and repeats of a face (either orientation), are dropped.  Every
+ * output is a pure function of the inputs (integers, and float64 with each operation rounded on its own):
+ * two runs are bit-identical and tests/mesh_simplify_ref.py restates the rule in numpy.  The rule in full,
+ * why each step is order-free and why the probe loop of the duplicate table ends: the header comment of
+ * nr_meshsimplify.hip.
+ *   verts fp32 [V, 3], faces int32 [F, 3] (device); 0 <= V <= INT32_MAX, 0 <= F <= 2^30.  h finite, > 0;
+ *   lo[3] (finite) and dim[3] (each >= 1, cells = dim[0] dim[1] dim[2] <= 2^27) are read on the host.
+ *   Per axis t = (x - lo) / h, c = clamp(floor(t), 0, dim - 1), cell = (c_z dim_y + c_y) dim_x + c_x.  A
+ *   cluster is an occupied cell, its id the rank of its cell among the occupied ones; output vertex k is
+ *   cluster k.  Its mean m: in-cell fractions quantised to 2^-20 of a cell and summed as integers.  Its
+ *   source vertex: the member with the smallest (|x - m|^2, index).
+ *   nr_mesh_simplify_workspace_bytes  with Kmax = min(V, cells) and T the power of two >= max(2 F, 64):
+ *                            256 + 4 cells + 4 ceil(cells / 256) + 4 V + Kmax (4 + 4 + 24 + 8 + 4 + 24)
+ *                            + 4 T + 4 F + 4 ceil(F / 256), every array rounded up to 256 bytes (0 on bad
+ *                            counts); one size serves both calls.
+ *   nr_mesh_simplify_count   bins, scans, accumulates, picks the representatives and marks the surviving
+ *                            faces.  totals (device int64 [3]) = {K clusters, F' surviving faces, status}:
+ *                            the one host read.  status bit 0: a face index outside [0, V) (the face is
+ *                            never dereferenced and does not survive); bit 1: the probe loop of the
+ *                            duplicate table reached its cap (cannot happen; results unusable); bit 2: a
+ *                            vertex coordinate is not finite (results unusable; nothing is accessed out of
+ *                            range).  The workspace then carries what nr_mesh_simplify_emit needs.
+ *   nr_mesh_simplify_emit    same verts / faces / counts / cells / workspace as the count before it; K / Fk
+ *                            the totals the caller read (K <= min(V, cells), Fk <= F, and the capacities
+ *                            verts_cap / faces_cap, in rows, must cover them: NR_ERR_ARG before any launch).
+ *                            position 0: verts_out [K, 3] = (float) m; 1: = verts[index[k]] unchanged.
+ *                            index int32 [K]: the source vertex; cluster_size int32 [K]: members;
+ *                            faces_out int32 [Fk, 3]: the surviving faces in input order, as cluster ids
+ *                            in their original order; vertex_cluster int32 [V].
+ * Argument errors (h <= 0, a dim < 1, more than 2^27 cells, null pointers: NR_ERR_ARG; a null or short
+ * workspace: NR_ERR_WORKSPACE) are reported before any GPU work.
+ * ------------------------------------------------------------------------------------------ */
+size_t nr_mesh_simplify_workspace_bytes(int64_t V, int64_t F, int64_t cells);
+int nr_mesh_simplify_count(const float* verts, int64_t V, const int32_t* faces, int64_t F, double h, const double* lo,
+                           const int64_t* dim, void* workspace, size_t workspace_bytes, int64_t* totals, void* stream);
+int nr_mesh_simplify_emit(const float* verts, int64_t V, const int32_t* faces, int64_t F, int64_t cells, int position,
+                          void* workspace, size_t workspace_bytes, int64_t K, int64_t Fk, float* verts_out,
+                          int32_t* index, int32_t* cluster_size, int64_t verts_cap, int32_t* faces_out,
+                          int64_t faces_cap, int32_t* vertex_cluster, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh rendering on the device (nr_meshrender.hip): depth, normals, barycentrics, face ids and a shaded
  * frame of an indexed triangle mesh, replacing the Open3D Visualizer pass of tools/render_view.py:438-486
  * (`--render_mesh`).  Pixel (i, j) = (column, row) is sampled exactly where nr_get_rays shoots its ray

@@ -235,6 +235,12 @@ _SIGS = {
     'nr_mesh_filter_count': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p, _c_p]),
     'nr_mesh_filter_emit': (_c_i, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_p, _c_i64, _c_p,
                                    _c_i64, _c_p]),
+    # mesh simplification by vertex clustering (nr_meshsimplify.hip)
+    'nr_mesh_simplify_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    'nr_mesh_simplify_count': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_d, ctypes.POINTER(_c_d), ctypes.POINTER(_c_i64),
+                                      _c_p, _c_sz, _c_p, _c_p]),
+    'nr_mesh_simplify_emit': (_c_i, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i, _c_p, _c_sz, _c_i64, _c_i64, _c_p, _c_p,
+                                     _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     # mesh rendering (nr_meshrender.hip)
     'nr_mesh_render_workspace_bytes': (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
     'nr_mesh_render': (_c_i, [ctypes.POINTER(NrMeshRenderArgs), _c_p]),

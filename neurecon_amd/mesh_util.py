@@ -30,7 +30,9 @@ components and drop the small ones, keeping the order of what stays (libnrhip `n
 maps a marching-cubes vertex back to the point of space the sheared grid above sampled;
 `vertex_attributes` evaluates normals (the SDF gradient) and colours (the radiance net, seen head-on) there
 with the render path's net kernels; `write_ply` carries both.  `extract_mesh`'s keywords keep / min_faces /
-vertex_normals / vertex_colors / coords chain them.
+vertex_normals / vertex_colors / coords chain them; `simplify` / `simplify_position` put
+`neurecon_amd.mesh_simplify.simplify_mesh` (vertex clustering, neurecon_amd/csrc/nr_meshsimplify.hip) between
+the filter and the attributes.
 
 Looking at the result, also on the device: `read_ply` reads the PLY back (the layouts `write_ply` writes, and
 the same elements as ASCII), `render_mesh` turns a mesh into a shaded frame, a depth map comparable with
@@ -654,7 +656,7 @@ def convert_sigma_samples_to_ply(input_3d_sigma_array, voxel_grid_origin, volume
 
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath='./surface.ply', show_progress=True,
                  chunk=16 * 1024, marching='auto', keep='all', min_faces=0, vertex_normals=False,
-                 vertex_colors=False, model=None, coords='reference'):
+                 vertex_colors=False, model=None, coords='reference', simplify=None, simplify_position='average'):
     """mesh_util.py:82-112, its quirks included: the grid is sampled with step s / (N - 1) but handed to
     marching cubes with spacing s / N and origin -s / 2 (:84, :112).  Writes `filepath`, returns None.
     `chunk` is accepted for API compatibility (the device grid uses larger launches).  On the native
@@ -666,13 +668,21 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath='
     UNISURF model that owns `implicit_surface`); coords='sampled' writes each vertex at the point of space
     the grid sampled (`grid_sample_positions`: the un-sheared, correctly scaled mesh) instead of the
     reference's s / N lattice.  Attributes are always evaluated at the sampled positions, whichever
-    coordinates are written.  Order: marching cubes, filter, attributes on the surviving vertices."""
+    coordinates are written.  Order: marching cubes, filter, attributes on the surviving vertices.
+
+    simplify=h (a cell size in world units, native marching only) runs `mesh_simplify.simplify_mesh` on the
+    written vertices after the component filter and before the attributes; simplify_position 'average' (the
+    cell's mean) or 'nearest' (the input vertex nearest to it).  With coords='sampled' the vertices live in
+    the model's space: given `model=` and 'average' they are first put back on the model's zero set by
+    `mesh_simplify.snap_to_surface`, and the attributes are evaluated at the written vertices.  With
+    coords='reference' (the sheared lattice) the attributes are evaluated at the sampled position of each
+    vertex's source vertex (`simplify_mesh`'s index), which lies on the iso-surface."""
     s = volume_size
     mode = _marching_mode(marching)
     if coords not in ('reference', 'sampled'):
         raise ValueError(f"coords must be 'reference' or 'sampled', got {coords!r}")
     options = dict(keep=keep != 'all', min_faces=min_faces != 0, vertex_normals=bool(vertex_normals),
-                   vertex_colors=bool(vertex_colors), coords=coords != 'reference')
+                   vertex_colors=bool(vertex_colors), coords=coords != 'reference', simplify=simplify is not None)
     used = [k for k, v in options.items() if v]
     if not used:
         out = sdf_grid(implicit_surface, s, N)
@@ -694,6 +704,12 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath='
         verts = grid_sample_positions(idx, s, N)
     del vol
     verts, faces, index = filter_mesh(verts, faces, keep=keep, min_faces=min_faces)
+    if simplify is not None:
+        from .mesh_simplify import simplify_mesh, snap_to_surface
+        verts, faces, src = simplify_mesh(verts, faces, simplify, position=simplify_position)
+        index = index.index_select(0, src)  # new vertex -> its source vertex among marching cubes'
+        if coords == 'sampled' and simplify_position == 'average' and model is not None:
+            verts = snap_to_surface(implicit_surface, verts)
     normals = colors = None
     if vertex_normals or vertex_colors:
         pos = verts if coords == 'sampled' else grid_sample_positions(idx.index_select(0, index), s, N)
