@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "nr_common.h"
+#include "nr_composite.h"
 #include "nr_mlp.h"
 #include "nr_neus.h"
 #include "nr_render.h"
@@ -17,15 +18,6 @@
 namespace nr {
 
 __device__ __forceinline__ float4 load3(const float* p) { return make_float4(p[0], p[1], p[2], 0.f); }
-
-// F.normalize(v, dim=-1): v / max(||v||_2, 1e-12)
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-  const float n = norm3_ref(x, y, z);
-  const float d = fmaxf(n, 1e-12f);
-  x = fdiv(x, d);
-  y = fdiv(y, d);
-  z = fdiv(z, d);
-}
 
 // ---------------------------------------------------------------------------------------------
 // prologue: normalize rays_d (neus.py:169-172), near/far (rend_util.py:167-185), coarse depths
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(64) void neus_upsample(NeusChunk c, int it, const f
     const float c1 = sigmoidf_ref(fmul(fadd(mid, md), S));
     const float alpha = fdiv(fadd(fsub(c0, c1), 1e-5f), fadd(c0, 1e-5f));
     sa[i] = alpha;
-    scdf[i] = fadd(fsub(1.0f, alpha), 1e-10f);  // the transmittance factor, off the serial chain
+    scdf[i] = transparency(alpha);  // the transmittance factor, off the serial chain
   }
   __syncthreads();
   if (l == 0 && live) {
@@ -315,14 +307,13 @@ __global__ __launch_bounds__(64) void neus_composite(NeusChunk c, NeusOut o, con
   float* snrm = srad + 3 * S; // [S-1][3] unit nablas
   float* sdm = snrm + 3 * S;  // [S-1] mid-point depths (the serial depth sum reads LDS, not HBM)
   for (int i = l; i < Sl; i += NL) {
-    const float cdf = sigmoidf_ref(fmul(c.sdf_f[i * R + r], s_inv));
+    const float cdf = neus_cdf(c.sdf_f[i * R + r], s_inv);
     scdf[i] = cdf;
     if (o.cdf) o.cdf[ro * S + i] = cdf;
   }
   __syncthreads();
   for (int i = l; i < Sl - 1; i += NL) {
-    const float cp = scdf[i], cn = scdf[i + 1];
-    const float alpha = fmaxf(fdiv(fsub(cp, cn), fadd(cp, 1e-10f)), 0.0f);
+    const float alpha = neus_alpha(scdf[i], scdf[i + 1]);
     sal[i] = alpha;
     if (o.alpha) o.alpha[ro * (S - 1) + i] = alpha;
     const int64_t q = i * R + r;
@@ -338,27 +329,15 @@ __global__ __launch_bounds__(64) void neus_composite(NeusChunk c, NeusOut o, con
     }
   }
   __syncthreads();
-  double rgb0 = 0.0, rgb1 = 0.0, rgb2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
-  float accf = 0.0f;
+  Composite A;
   if (l == 0 && live) {
-    double T = 1.0, acc = 0.0;
     for (int i = 0; i < S - 1; ++i) {
-      const float alpha = sal[i];
-      const float w = fmul(alpha, (float)T);
-      T *= (double)fadd(fsub(1.0f, alpha), 1e-10f);
-      rgb0 += (double)fmul(w, srad[i * 3 + 0]);
-      rgb1 += (double)fmul(w, srad[i * 3 + 1]);
-      rgb2 += (double)fmul(w, srad[i * 3 + 2]);
-      acc += (double)w;
-      if (calc_normal) {
-        n0 += (double)fmul(snrm[i * 3 + 0], w);
-        n1 += (double)fmul(snrm[i * 3 + 1], w);
-        n2 += (double)fmul(snrm[i * 3 + 2], w);
-      }
+      const float w = A.weight(sal[i]);
+      A.add(w, srad + i * 3);
+      if (calc_normal) A.add_normal(w, snrm[i * 3 + 0], snrm[i * 3 + 1], snrm[i * 3 + 2]);
       sal[i] = w;
     }
-    accf = (float)acc;
-    scdf[0] = fadd(accf, 1e-10f);  // the depth normaliser for the ray's lanes (the cdf is no longer read)
+    scdf[0] = A.denom();  // the depth normaliser for the ray's lanes (the cdf is no longer read)
   }
   __syncthreads();
   // depth terms w_i / (acc + 1e-10) * d_mid_i across the ray's lanes, into scdf[1 ..] (the CDFs
@@ -372,40 +351,18 @@ __global__ __launch_bounds__(64) void neus_composite(NeusChunk c, NeusOut o, con
   if (l == 0 && live) {
     double depth = 0.0;
     for (int i = 0; i < S - 1; ++i) depth += (double)scdf[i + 1];
-    float r0 = (float)rgb0, r1 = (float)rgb1, r2 = (float)rgb2;
-    if (white_bkgd) {
-      const float bg = fsub(1.0f, accf);
-      r0 = fadd(r0, bg); r1 = fadd(r1, bg); r2 = fadd(r2, bg);
-    }
-    o.rgb[ro * 3 + 0] = r0;
-    o.rgb[ro * 3 + 1] = r1;
-    o.rgb[ro * 3 + 2] = r2;
-    o.depth[ro] = (float)depth;
-    o.acc[ro] = accf;
-    if (calc_normal && o.normals) {
-      o.normals[ro * 3 + 0] = (float)n0;
-      o.normals[ro * 3 + 1] = (float)n1;
-      o.normals[ro * 3 + 2] = (float)n2;
-    }
+    A.finish((float)depth, white_bkgd, ro, o.rgb, o.depth, o.acc, calc_normal ? o.normals : nullptr);
   }
   __syncthreads();
   // detailed per-sample outputs, ray-major
   for (int i = l; i < Sl; i += NL) {
     const int64_t q = i * R + r;
     if (o.sdf) o.sdf[ro * S + i] = c.sdf_f[q];
-    if (o.nablas) {
-      o.nablas[(ro * S + i) * 3 + 0] = c.nab_f[q * 3 + 0];
-      o.nablas[(ro * S + i) * 3 + 1] = c.nab_f[q * 3 + 1];
-      o.nablas[(ro * S + i) * 3 + 2] = c.nab_f[q * 3 + 2];
-    }
+    if (o.nablas) copy3(o.nablas + (ro * S + i) * 3, c.nab_f + q * 3);
     if (i < S - 1) {
       if (o.weights) o.weights[ro * (S - 1) + i] = sal[i];
       if (o.d_final) o.d_final[ro * (S - 1) + i] = c.dmid[q];
-      if (o.radiance) {
-        o.radiance[(ro * (S - 1) + i) * 3 + 0] = srad[i * 3 + 0];
-        o.radiance[(ro * (S - 1) + i) * 3 + 1] = srad[i * 3 + 1];
-        o.radiance[(ro * (S - 1) + i) * 3 + 2] = srad[i * 3 + 2];
-      }
+      if (o.radiance) copy3(o.radiance + (ro * (S - 1) + i) * 3, srad + i * 3);
     }
   }
 }
@@ -453,12 +410,12 @@ __global__ __launch_bounds__(64) void neus_direct_upsample(NeusChunk c, int more
   const float* sdf = more ? c.s_nog + r : c.sv + r;
   // sdf_to_w (neus.py:37-70): logistic cdf, alpha = max((c_i - c_i+1)/(c_i + 1e-10), 0), cumprod
   double T = 1.0;
-  float cprev = sigmoidf_ref(fmul(sdf[0], c.fixed_s));
+  float cprev = neus_cdf(sdf[0], c.fixed_s);
   for (int i = 0; i < L - 1; ++i) {
-    const float cn = sigmoidf_ref(fmul(sdf[(int64_t)(i + 1) * R], c.fixed_s));
-    const float alpha = fmaxf(fdiv(fsub(cprev, cn), fadd(cprev, 1e-10f)), 0.0f);
+    const float cn = neus_cdf(sdf[(int64_t)(i + 1) * R], c.fixed_s);
+    const float alpha = neus_alpha(cprev, cn);
     c.wtmp[(int64_t)i * R + r] = fmul(alpha, (float)T);
-    T *= (double)fadd(fsub(1.0f, alpha), 1e-10f);
+    T *= (double)transparency(alpha);
     cprev = cn;
   }
   float* wr = c.wtmp + r;
@@ -556,7 +513,7 @@ __device__ __forceinline__ int64_t block_append(bool need, int* __restrict__ cou
 // mid-points outside the bounding sphere -- the ones inside take the SDF's alpha and radiance, so the
 // reference's background evaluation there is discarded.  Without detailed outputs only these points
 // go through the NeRF++ net: appended (one atomic per workgroup) to x4c / vdc, slot[q] = compact index or
-// -1; the inside test is the compositing's own (norm3_ref(o + d dm) <= r_obj).
+// -1.
 __global__ void neus_outside_compact(NeusChunk c, int* __restrict__ count, int* __restrict__ slot,
                                      float* __restrict__ x4c, float* __restrict__ vdc) {
   const int64_t R = c.R;
@@ -571,10 +528,7 @@ __global__ void neus_outside_compact(NeusChunk c, int* __restrict__ count, int* 
     if (k >= S1) {
       need = true;
     } else {
-      const float dm = c.dmid[q];
-      const float px = fadd(c.ro[r * 3], fmul(c.rd[r * 3], dm)), py = fadd(c.ro[r * 3 + 1], fmul(c.rd[r * 3 + 1], dm)),
-                  pz = fadd(c.ro[r * 3 + 2], fmul(c.rd[r * 3 + 2], dm));
-      need = !(norm3_ref(px, py, pz) <= c.r_obj);
+      need = !inside_sphere(c.ro, c.rd, r, c.dmid[q], c.r_obj);
     }
   }
   const int64_t ja = block_append(need, count);
@@ -594,8 +548,8 @@ __global__ void neus_outside_compact(NeusChunk c, int* __restrict__ count, int* 
 // Mid-point i of a ray contributes w_i * radiance_i with w_i = alpha_i T_i, and alpha_i = max((c_i -
 // c_{i+1}) / (c_i + 1e-10), 0) is exactly 0 wherever the SDF does not decrease from sample i to i+1
 // (neus.py:28-35): there the radiance (and the mid-point's SDF, nablas and feature that feed it) is
-// multiplied by an exact zero.  Without detailed outputs only the mid-points with alpha != 0 (the
-// compositing's own arithmetic) go through the SDF + radiance nets; the others get radiance 0.
+// multiplied by an exact zero.  Without detailed outputs only the mid-points with alpha != 0
+// (neus_alpha, as the compositing forms it) go through the SDF + radiance nets; the others get radiance 0.
 __global__ void neus_mid_compact(NeusChunk c, const float* __restrict__ s_dev, float s_val, int* __restrict__ count,
                                  int* __restrict__ slot, float* __restrict__ midc, float* __restrict__ vdc) {
   const int64_t R = c.R;
@@ -608,16 +562,11 @@ __global__ void neus_mid_compact(NeusChunk c, const float* __restrict__ s_dev, f
     const float s_inv = s_dev ? *s_dev : s_val;
     const int i = (int)(q / R);
     r = q - (int64_t)i * R;
-    const float cp = sigmoidf_ref(fmul(c.sdf_f[(int64_t)i * R + r], s_inv));
-    const float cn = sigmoidf_ref(fmul(c.sdf_f[(int64_t)(i + 1) * R + r], s_inv));
-    const float alpha = fmaxf(fdiv(fsub(cp, cn), fadd(cp, 1e-10f)), 0.0f);
-    need = !(alpha == 0.0f);
-    if (need && c.N_out > 0) {  // NeRF++: a mid-point outside the bounding sphere takes the background's
-      const float dm = c.dmid[q];  // alpha and colour (neus_composite_outside's own inside test)
-      const float px = fadd(c.ro[r * 3], fmul(c.rd[r * 3], dm)), py = fadd(c.ro[r * 3 + 1], fmul(c.rd[r * 3 + 1], dm)),
-                  pz = fadd(c.ro[r * 3 + 2], fmul(c.rd[r * 3 + 2], dm));
-      need = norm3_ref(px, py, pz) <= c.r_obj;
-    }
+    const float cp = neus_cdf(c.sdf_f[(int64_t)i * R + r], s_inv);
+    const float cn = neus_cdf(c.sdf_f[(int64_t)(i + 1) * R + r], s_inv);
+    need = !(neus_alpha(cp, cn) == 0.0f);
+    // NeRF++: a mid-point outside the bounding sphere takes the background's alpha and colour
+    if (need && c.N_out > 0) need = inside_sphere(c.ro, c.rd, r, c.dmid[q], c.r_obj);
   }
   const int64_t j = block_append(need, count);
   if (!in_range) return;
@@ -633,13 +582,9 @@ __global__ void neus_mid_compact(NeusChunk c, const float* __restrict__ s_dev, f
   }
 }
 
-// F.softplus (beta 1, threshold 20)
-__device__ __forceinline__ float softplus1(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-
 // deferred sample nablas: flag the 16-slot tile (evaluation order) of every sorted sample i < S-1 whose
 // interval alpha is not exactly 0 -- neus_composite weights sample i's unit nabla by w_i = alpha_i T_i
 // (neus.py:364-368), so the others contribute exactly 0 (their nablas stay 0, normalize(0) = 0).
-// Same alpha arithmetic as neus_mid_compact / the compositing.
 __global__ void neus_sample_need(NeusChunk c, const float* __restrict__ s_dev, float s_val) {
   const int64_t R = c.R;
   const int S1 = c.S - 1;
@@ -648,17 +593,16 @@ __global__ void neus_sample_need(NeusChunk c, const float* __restrict__ s_dev, f
   const float s_inv = s_dev ? *s_dev : s_val;
   const int i = (int)(q / R);
   const int64_t r = q - (int64_t)i * R;
-  const float cp = sigmoidf_ref(fmul(c.sdf_f[(int64_t)i * R + r], s_inv));
-  const float cn = sigmoidf_ref(fmul(c.sdf_f[(int64_t)(i + 1) * R + r], s_inv));
-  const float alpha = fmaxf(fdiv(fsub(cp, cn), fadd(cp, 1e-10f)), 0.0f);
-  if (!(alpha == 0.0f)) c.tflag[((int64_t)c.idv[q] * R + r) >> c.tshift] = 1;
+  const float cp = neus_cdf(c.sdf_f[(int64_t)i * R + r], s_inv);
+  const float cn = neus_cdf(c.sdf_f[(int64_t)(i + 1) * R + r], s_inv);
+  if (!(neus_alpha(cp, cn) == 0.0f)) c.tflag[((int64_t)c.idv[q] * R + r) >> c.tshift] = 1;
 }
 
 // the same with the NeRF++ background (neus_composite_outside): sample k < S weights its unit nabla by
 // w_k = alpha_k T_k, alpha_k the SDF alpha of interval k if mid-point k is inside the bounding sphere,
 // else the background's 1 - exp(-softplus(sigma) dist) -- also for k = S-1, whose weight is the first
 // inverted-sphere sample's (neus.py:364-366 pairs min(#weights, #nablas) = S of them).  Runs after the
-// background net (sig_o) with the compositing's own arithmetic; a tile is flagged if any alpha != 0.
+// background net (sig_o); a tile is flagged if any alpha != 0.
 __global__ void neus_sample_need_outside(NeusChunk c, const float* __restrict__ s_dev, float s_val) {
   const int64_t R = c.R;
   const int S = c.S, S1 = S - 1, M = S1 + c.N_out;
@@ -670,18 +614,14 @@ __global__ void neus_sample_need_outside(NeusChunk c, const float* __restrict__ 
   float alpha = 0.0f;
   if (k < S1) {
     const float s_inv = s_dev ? *s_dev : s_val;
-    const float cp = sigmoidf_ref(fmul(c.sdf_f[(int64_t)k * R + r], s_inv));
-    const float cn = sigmoidf_ref(fmul(c.sdf_f[(int64_t)(k + 1) * R + r], s_inv));
-    alpha = fmaxf(fdiv(fsub(cp, cn), fadd(cp, 1e-10f)), 0.0f);
-    const float dm = c.dmid[q];
-    const float px = fadd(c.ro[r * 3], fmul(c.rd[r * 3], dm)), py = fadd(c.ro[r * 3 + 1], fmul(c.rd[r * 3 + 1], dm)),
-                pz = fadd(c.ro[r * 3 + 2], fmul(c.rd[r * 3 + 2], dm));
-    inside = norm3_ref(px, py, pz) <= c.r_obj;
+    const float cp = neus_cdf(c.sdf_f[(int64_t)k * R + r], s_inv);
+    const float cn = neus_cdf(c.sdf_f[(int64_t)(k + 1) * R + r], s_inv);
+    alpha = neus_alpha(cp, cn);
+    inside = inside_sphere(c.ro, c.rd, r, c.dmid[q], c.r_obj);
   }
   if (!inside) {
-    const float dk = c.d_out[q];
-    const float dist = k + 1 < M ? fsub(c.d_out[q + R], dk) : 1e10f;
-    alpha = fsub(1.0f, expf(fmul(-softplus1(c.sig_o[q]), dist)));
+    const float dist = nerfpp_dist(c.d_out[q], c.d_out, q + R, k + 1 < M);
+    alpha = nerfpp_alpha(c.sig_o[q], dist);
   }
   if (!(alpha == 0.0f)) c.tflag[((int64_t)c.idv[q] * R + r) >> c.tshift] = 1;
 }
@@ -749,8 +689,8 @@ __global__ void neus_outside_scatter(const int* __restrict__ slot, const float* 
 // compositing with the background merged in, RPW rays per wave (neus_composite's structure): the
 // per-sample CDFs, the inside test, the inside / background alphas, radiance and unit nablas across the
 // ray's lanes into LDS; the transmittance product and the fp64 sums on the ray's first lane in sample
-// order with the per-ray version's arithmetic (bit-identical maps; that version, one thread per ray,
-// remains the fallback when the LDS staging does not fit).  LDS per ray: 6 M + 4 S floats.
+// order (neus_composite_outside, one thread per ray, remains the fallback when the LDS staging does not
+// fit).  LDS per ray: 6 M + 4 S floats.
 template <int RPW>
 __global__ __launch_bounds__(64) void neus_composite_outside_w(NeusChunk c, NeusOut o, const float* __restrict__ s_dev,
                                                                float s_val, int calc_normal, int white_bkgd) {
@@ -771,7 +711,7 @@ __global__ __launch_bounds__(64) void neus_composite_outside_w(NeusChunk c, Neus
   float* dum = sdo + M;        // [M] (pad)
   float* snrm = dum + M;       // [S][3] unit nablas
   for (int i = l; i < Sl; i += NL) {
-    const float cdf = sigmoidf_ref(fmul(c.sdf_f[(int64_t)i * R + r], s_inv));
+    const float cdf = neus_cdf(c.sdf_f[(int64_t)i * R + r], s_inv);
     scdf[i] = cdf;
     if (o.cdf) o.cdf[ro * S + i] = cdf;
   }
@@ -783,12 +723,8 @@ __global__ __launch_bounds__(64) void neus_composite_outside_w(NeusChunk c, Neus
     bool inside = false;
     float a_in = 0.0f;
     if (k < S1) {
-      const float cp = scdf[k], cn = scdf[k + 1];
-      a_in = fmaxf(fdiv(fsub(cp, cn), fadd(cp, 1e-10f)), 0.0f);
-      const float dm = c.dmid[q];
-      const float px = fadd(c.ro[r * 3], fmul(c.rd[r * 3], dm)), py = fadd(c.ro[r * 3 + 1], fmul(c.rd[r * 3 + 1], dm)),
-                  pz = fadd(c.ro[r * 3 + 2], fmul(c.rd[r * 3 + 2], dm));
-      inside = norm3_ref(px, py, pz) <= c.r_obj;
+      a_in = neus_alpha(scdf[k], scdf[k + 1]);
+      inside = inside_sphere(c.ro, c.rd, r, c.dmid[q], c.r_obj);
     }
     float alpha;
     if (inside) {
@@ -796,8 +732,8 @@ __global__ __launch_bounds__(64) void neus_composite_outside_w(NeusChunk c, Neus
 #pragma unroll
       for (int e = 0; e < 3; ++e) srad[k * 3 + e] = c.rad_m[q * 3 + e];
     } else {
-      const float dist = k + 1 < M ? fsub(c.d_out[q + R], dk) : 1e10f;
-      alpha = fsub(1.0f, expf(fmul(-softplus1(c.sig_o[q]), dist)));
+      const float dist = nerfpp_dist(dk, c.d_out, q + R, k + 1 < M);
+      alpha = nerfpp_alpha(c.sig_o[q], dist);
 #pragma unroll
       for (int e = 0; e < 3; ++e) srad[k * 3 + e] = c.rad_o[q * 3 + e];
     }
@@ -816,41 +752,17 @@ __global__ __launch_bounds__(64) void neus_composite_outside_w(NeusChunk c, Neus
   }
   __syncthreads();
   if (l == 0 && live) {
-    double T = 1.0, acc = 0.0, rgb0 = 0.0, rgb1 = 0.0, rgb2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
+    Composite A;
     for (int k = 0; k < M; ++k) {
-      const float alpha = sal[k];
-      const float w = fmul(alpha, (float)T);
-      T *= (double)fadd(fsub(1.0f, alpha), 1e-10f);
-      rgb0 += (double)fmul(w, srad[k * 3 + 0]);
-      rgb1 += (double)fmul(w, srad[k * 3 + 1]);
-      rgb2 += (double)fmul(w, srad[k * 3 + 2]);
-      acc += (double)w;
-      if (calc_normal && k < Nn) {
-        n0 += (double)fmul(snrm[k * 3 + 0], w);
-        n1 += (double)fmul(snrm[k * 3 + 1], w);
-        n2 += (double)fmul(snrm[k * 3 + 2], w);
-      }
+      const float w = A.weight(sal[k]);
+      A.add(w, srad + k * 3);
+      if (calc_normal && k < Nn) A.add_normal(w, snrm[k * 3 + 0], snrm[k * 3 + 1], snrm[k * 3 + 2]);
       sal[k] = w;
     }
-    const float accf = (float)acc;
-    const float denom = fadd(accf, 1e-10f);
+    const float denom = A.denom();
     double depth = 0.0;
     for (int k = 0; k < M; ++k) depth += (double)fmul(fdiv(sal[k], denom), sdo[k]);
-    float q0 = (float)rgb0, q1 = (float)rgb1, q2 = (float)rgb2;
-    if (white_bkgd) {
-      const float bg = fsub(1.0f, accf);
-      q0 = fadd(q0, bg); q1 = fadd(q1, bg); q2 = fadd(q2, bg);
-    }
-    o.rgb[ro * 3 + 0] = q0;
-    o.rgb[ro * 3 + 1] = q1;
-    o.rgb[ro * 3 + 2] = q2;
-    o.depth[ro] = (float)depth;
-    o.acc[ro] = accf;
-    if (calc_normal && o.normals) {
-      o.normals[ro * 3 + 0] = (float)n0;
-      o.normals[ro * 3 + 1] = (float)n1;
-      o.normals[ro * 3 + 2] = (float)n2;
-    }
+    A.finish((float)depth, white_bkgd, ro, o.rgb, o.depth, o.acc, calc_normal ? o.normals : nullptr);
   }
   __syncthreads();
   // detailed per-sample outputs, ray-major
@@ -858,26 +770,14 @@ __global__ __launch_bounds__(64) void neus_composite_outside_w(NeusChunk c, Neus
     const int64_t q = (int64_t)k * R + r;
     if (o.weights) o.weights[ro * M + k] = sal[k];
     if (o.d_final) o.d_final[ro * M + k] = sdo[k];
-    if (o.radiance) {
-      o.radiance[(ro * M + k) * 3 + 0] = srad[k * 3 + 0];
-      o.radiance[(ro * M + k) * 3 + 1] = srad[k * 3 + 1];
-      o.radiance[(ro * M + k) * 3 + 2] = srad[k * 3 + 2];
-    }
+    if (o.radiance) copy3(o.radiance + (ro * M + k) * 3, srad + k * 3);
     if (o.sigma_out) o.sigma_out[ro * M + k] = c.sig_o[q];
-    if (o.radiance_bg) {
-      o.radiance_bg[(ro * M + k) * 3 + 0] = c.rad_o[q * 3 + 0];
-      o.radiance_bg[(ro * M + k) * 3 + 1] = c.rad_o[q * 3 + 1];
-      o.radiance_bg[(ro * M + k) * 3 + 2] = c.rad_o[q * 3 + 2];
-    }
+    if (o.radiance_bg) copy3(o.radiance_bg + (ro * M + k) * 3, c.rad_o + q * 3);
   }
   for (int i = l; i < Sl; i += NL) {
     const int64_t q = (int64_t)i * R + r;
     if (o.sdf) o.sdf[ro * S + i] = c.sdf_f[q];
-    if (o.nablas) {
-      o.nablas[(ro * S + i) * 3 + 0] = c.nab_f[q * 3 + 0];
-      o.nablas[(ro * S + i) * 3 + 1] = c.nab_f[q * 3 + 1];
-      o.nablas[(ro * S + i) * 3 + 2] = c.nab_f[q * 3 + 2];
-    }
+    if (o.nablas) copy3(o.nablas + (ro * S + i) * 3, c.nab_f + q * 3);
   }
 }
 
@@ -893,96 +793,61 @@ __global__ __launch_bounds__(64) void neus_composite_outside(NeusChunk c, NeusOu
   const int S = c.S, S1 = S - 1, M = S1 + c.N_out;
   const int64_t R = c.R;
   const int64_t ro = o.ray0 + r;
-  const float ox = c.ro[r * 3], oy = c.ro[r * 3 + 1], oz = c.ro[r * 3 + 2];
-  const float dx = c.rd[r * 3], dy = c.rd[r * 3 + 1], dz = c.rd[r * 3 + 2];
-  double T = 1.0, acc = 0.0, rgb0 = 0.0, rgb1 = 0.0, rgb2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
-  float cprev = sigmoidf_ref(fmul(c.sdf_f[r], s_inv));
+  const float ro3[3] = {c.ro[r * 3], c.ro[r * 3 + 1], c.ro[r * 3 + 2]};
+  const float rd3[3] = {c.rd[r * 3], c.rd[r * 3 + 1], c.rd[r * 3 + 2]};
+  Composite A;
+  float cprev = neus_cdf(c.sdf_f[r], s_inv);
   if (o.cdf) o.cdf[ro * S] = cprev;
   const int Nn = M < S ? M : S;  // normals use min(#weights, #nablas) samples (neus.py:364-366)
   for (int k = 0; k < M; ++k) {
     const int64_t q = (int64_t)k * R + r;
     const float dk = c.d_out[q];
-    const float dist = k + 1 < M ? fsub(c.d_out[q + R], dk) : 1e10f;
-    const float a_out = fsub(1.0f, expf(fmul(-softplus1(c.sig_o[q]), dist)));
-    float alpha, r0, r1, r2;
+    const float dist = nerfpp_dist(dk, c.d_out, q + R, k + 1 < M);
+    const float a_out = nerfpp_alpha(c.sig_o[q], dist);
+    float alpha, col[3];
     bool inside = false;
     float a_in = 0.f;
     if (k < S1) {
-      const float cn = sigmoidf_ref(fmul(c.sdf_f[(int64_t)(k + 1) * R + r], s_inv));
-      a_in = fmaxf(fdiv(fsub(cprev, cn), fadd(cprev, 1e-10f)), 0.0f);
+      const float cn = neus_cdf(c.sdf_f[(int64_t)(k + 1) * R + r], s_inv);
+      a_in = neus_alpha(cprev, cn);
       if (o.cdf) o.cdf[ro * S + k + 1] = cn;
       cprev = cn;
-      const float dm = c.dmid[q];
-      const float px = fadd(ox, fmul(dx, dm)), py = fadd(oy, fmul(dy, dm)), pz = fadd(oz, fmul(dz, dm));
-      inside = norm3_ref(px, py, pz) <= c.r_obj;
+      inside = inside_sphere(ro3, rd3, 0, c.dmid[q], c.r_obj);
     }
     if (inside) {
       alpha = a_in;
-      r0 = c.rad_m[q * 3 + 0]; r1 = c.rad_m[q * 3 + 1]; r2 = c.rad_m[q * 3 + 2];
+      col[0] = c.rad_m[q * 3 + 0]; col[1] = c.rad_m[q * 3 + 1]; col[2] = c.rad_m[q * 3 + 2];
     } else {
       alpha = a_out;
-      r0 = c.rad_o[q * 3 + 0]; r1 = c.rad_o[q * 3 + 1]; r2 = c.rad_o[q * 3 + 2];
+      col[0] = c.rad_o[q * 3 + 0]; col[1] = c.rad_o[q * 3 + 1]; col[2] = c.rad_o[q * 3 + 2];
     }
-    const float w = fmul(alpha, (float)T);
-    T *= (double)fadd(fsub(1.0f, alpha), 1e-10f);
-    rgb0 += (double)fmul(w, r0);
-    rgb1 += (double)fmul(w, r1);
-    rgb2 += (double)fmul(w, r2);
-    acc += (double)w;
+    const float w = A.weight(alpha);
+    A.add(w, col);
     if (calc_normal && k < Nn) {
       float x = c.nab_f[(int64_t)k * R * 3 + r * 3 + 0], y = c.nab_f[(int64_t)k * R * 3 + r * 3 + 1],
             z = c.nab_f[(int64_t)k * R * 3 + r * 3 + 2];
       normalize3(x, y, z);
-      n0 += (double)fmul(x, w);
-      n1 += (double)fmul(y, w);
-      n2 += (double)fmul(z, w);
+      A.add_normal(w, x, y, z);
     }
     c.wtmp[q] = w;
     if (o.alpha) o.alpha[ro * M + k] = alpha;
     if (o.weights) o.weights[ro * M + k] = w;
     if (o.d_final) o.d_final[ro * M + k] = dk;
-    if (o.radiance) {
-      o.radiance[(ro * M + k) * 3 + 0] = r0;
-      o.radiance[(ro * M + k) * 3 + 1] = r1;
-      o.radiance[(ro * M + k) * 3 + 2] = r2;
-    }
+    if (o.radiance) copy3(o.radiance + (ro * M + k) * 3, col);
     if (o.sigma_out) o.sigma_out[ro * M + k] = c.sig_o[q];
-    if (o.radiance_bg) {
-      o.radiance_bg[(ro * M + k) * 3 + 0] = c.rad_o[q * 3 + 0];
-      o.radiance_bg[(ro * M + k) * 3 + 1] = c.rad_o[q * 3 + 1];
-      o.radiance_bg[(ro * M + k) * 3 + 2] = c.rad_o[q * 3 + 2];
-    }
+    if (o.radiance_bg) copy3(o.radiance_bg + (ro * M + k) * 3, c.rad_o + q * 3);
   }
-  const float accf = (float)acc;
-  const float denom = fadd(accf, 1e-10f);
+  const float denom = A.denom();
   double depth = 0.0;
   for (int k = 0; k < M; ++k) {
     const int64_t q = (int64_t)k * R + r;
     depth += (double)fmul(fdiv(c.wtmp[q], denom), c.d_out[q]);
   }
-  float q0 = (float)rgb0, q1 = (float)rgb1, q2 = (float)rgb2;
-  if (white_bkgd) {
-    const float bg = fsub(1.0f, accf);
-    q0 = fadd(q0, bg); q1 = fadd(q1, bg); q2 = fadd(q2, bg);
-  }
-  o.rgb[ro * 3 + 0] = q0;
-  o.rgb[ro * 3 + 1] = q1;
-  o.rgb[ro * 3 + 2] = q2;
-  o.depth[ro] = (float)depth;
-  o.acc[ro] = accf;
-  if (calc_normal && o.normals) {
-    o.normals[ro * 3 + 0] = (float)n0;
-    o.normals[ro * 3 + 1] = (float)n1;
-    o.normals[ro * 3 + 2] = (float)n2;
-  }
+  A.finish((float)depth, white_bkgd, ro, o.rgb, o.depth, o.acc, calc_normal ? o.normals : nullptr);
   for (int i = 0; i < S; ++i) {
     const int64_t q = (int64_t)i * R + r;
     if (o.sdf) o.sdf[ro * S + i] = c.sdf_f[q];
-    if (o.nablas) {
-      o.nablas[(ro * S + i) * 3 + 0] = c.nab_f[q * 3 + 0];
-      o.nablas[(ro * S + i) * 3 + 1] = c.nab_f[q * 3 + 1];
-      o.nablas[(ro * S + i) * 3 + 2] = c.nab_f[q * 3 + 2];
-    }
+    if (o.nablas) copy3(o.nablas + (ro * S + i) * 3, c.nab_f + q * 3);
   }
 }
 

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "nr_common.h"
+#include "nr_composite.h"
 
 namespace nr {
 namespace {
@@ -371,35 +372,13 @@ __global__ void neus_points_kernel(const float* __restrict__ ro, const float* __
 
 // NeuS compositing with a differentiable graph (neus.py:28-70, :346-355), one thread per ray.
 // sdf [R,S], radiance [R,S-1,3], dmid [R,S-1]; s from the device.  fp64 prefix products / sums
-// rounded per element, as in the render kernels.
+// rounded per element (nr_composite.h).
 // One ray per 64-lane wave, everything across the lanes (r05; r03-r04 ran the scans on lane 0: 26 + 78
 // us per 512-ray step): the transmittance T_i = prod_{j<i} (1 - alpha_j + 1e-10) is a wave prefix
 // product in fp64 over 64-sample segments with a carried running product, the colour / opacity / depth
 // sums are per-lane fp64 partials reduced by a fixed butterfly; the backward's suffix sums likewise.
 // The association of the fp64 products and sums differs from a sequential walk (relative 1e-16, below
 // the per-element fp32 rounding).  LDS: fwd 2 S floats, bwd S doubles + 5 S floats.
-__device__ __forceinline__ double wave_incl_prod(double x, int l) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double t = __shfl_up(x, d);
-    if (l >= d) x *= t;
-  }
-  return x;
-}
-__device__ __forceinline__ double wave_incl_sum_rev(double x, int l) {  // sum over lanes >= l
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double t = __shfl_down(x, d);
-    if (l + d < 64) x += t;
-  }
-  return x;
-}
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 __global__ __launch_bounds__(64) void neus_composite_fwd_kernel(const float* __restrict__ sdf, const float* __restrict__ s_dev,
                                           const float* __restrict__ rad, const float* __restrict__ dmid, int64_t R,
                                           int S, int white_bkgd, float* __restrict__ rgb, float* __restrict__ depth,
@@ -413,57 +392,43 @@ __global__ __launch_bounds__(64) void neus_composite_fwd_kernel(const float* __r
   float* lc = lds;      // [S] cdf
   float* lw = lc + S;   // [S] weights
   for (int i = l; i < S; i += 64) {
-    const float c = sigmoidf_ref(fmul(sd[i], s));
+    const float c = neus_cdf(sd[i], s);
     lc[i] = c;
     if (cdf_out) cdf_out[r * S + i] = c;
   }
   __syncthreads();
-  double Tc = 1.0, c0 = 0.0, c1 = 0.0, c2 = 0.0, a_acc = 0.0;
+  double Tc = 1.0;
+  Composite A;  // this lane's partial sums (its T is not stepped: the wave scan gives T)
   for (int b = 0; b < S1; b += 64) {
     const int i = b + l;
     const bool ok = i < S1;
     const int64_t q = r * S1 + (ok ? i : 0);
-    const float al = ok ? fmaxf(fdiv(fsub(lc[i], lc[i + 1]), fadd(lc[i], 1e-10f)), 0.0f) : 0.0f;
-    const double u = ok ? (double)fadd(fsub(1.0f, al), 1e-10f) : 1.0;
-    const double incl = wave_incl_prod(u, l);
+    const float al = ok ? neus_alpha(lc[i], lc[i + 1]) : 0.0f;
+    const double u = ok ? (double)transparency(al) : 1.0;
+    const double incl = wave_scan_mul(u);
     const double excl = __shfl_up(incl, 1);
     const double T = Tc * (l == 0 ? 1.0 : excl);
     const float w = fmul(al, (float)T);
     if (ok) {
       lw[i] = w;
       if (alpha_out) alpha_out[q] = al;
-      c0 += (double)fmul(w, rad[q * 3 + 0]);
-      c1 += (double)fmul(w, rad[q * 3 + 1]);
-      c2 += (double)fmul(w, rad[q * 3 + 2]);
-      a_acc += (double)w;
+      A.add(w, rad + q * 3);
     }
     Tc *= __shfl(incl, 63);
   }
-  c0 = wave_sum_d(c0);
-  c1 = wave_sum_d(c1);
-  c2 = wave_sum_d(c2);
-  a_acc = wave_sum_d(a_acc);
+  A.c0 = wave_sum(A.c0);
+  A.c1 = wave_sum(A.c1);
+  A.c2 = wave_sum(A.c2);
+  A.acc = wave_sum(A.acc);
   __syncthreads();
-  const float accf = (float)a_acc;
-  const float den = fadd(accf, 1e-10f);
+  const float den = A.denom();
   double dep = 0.0;
   for (int i = l; i < S1; i += 64) {
     dep += (double)fmul(fdiv(lw[i], den), dmid[r * S1 + i]);
     w_out[r * S1 + i] = lw[i];
   }
-  dep = wave_sum_d(dep);
-  if (l == 0) {
-    float o0 = (float)c0, o1 = (float)c1, o2 = (float)c2;
-    if (white_bkgd) {
-      const float bg = fsub(1.0f, accf);
-      o0 = fadd(o0, bg); o1 = fadd(o1, bg); o2 = fadd(o2, bg);
-    }
-    rgb[r * 3 + 0] = o0;
-    rgb[r * 3 + 1] = o1;
-    rgb[r * 3 + 2] = o2;
-    depth[r] = (float)dep;
-    acc[r] = accf;
-  }
+  dep = wave_sum(dep);
+  if (l == 0) A.finish((float)dep, white_bkgd, r, rgb, depth, acc, nullptr);
 }
 
 // backward of the above: grads of rgb [R,3], depth [R], acc [R] and (optional) the visibility
@@ -489,46 +454,38 @@ __global__ __launch_bounds__(64) void neus_composite_bwd_kernel(const float* __r
   float* Tt = al + S;     // [S] T (fp32, as the weights use it)
   float* wb = Tt + S;     // [S] weight adjoints
   float* cib = wb + S;    // [S] ci_bar (fp32)
-  for (int i = l; i < S; i += 64) c[i] = sigmoidf_ref(fmul(sd[i], s));
+  for (int i = l; i < S; i += 64) c[i] = neus_cdf(sd[i], s);
   __syncthreads();
   // forward recompute: alpha, T, weights; acc and sum w d
-  double Tc = 1.0, a_acc = 0.0, wd = 0.0;
+  double Tc = 1.0, wd = 0.0;
+  Composite F;  // the forward again: this lane's partial opacity
   for (int b = 0; b < S1; b += 64) {
     const int i = b + l;
     const bool ok = i < S1;
-    const float a = ok ? fmaxf(fdiv(fsub(c[i], c[i + 1]), fadd(c[i], 1e-10f)), 0.0f) : 0.0f;
-    const double u = ok ? (double)fadd(fsub(1.0f, a), 1e-10f) : 1.0;
-    const double incl = wave_incl_prod(u, l);
+    const float a = ok ? neus_alpha(c[i], c[i + 1]) : 0.0f;
+    const double u = ok ? (double)transparency(a) : 1.0;
+    const double incl = wave_scan_mul(u);
     const double excl = __shfl_up(incl, 1);
     const float T = (float)(Tc * (l == 0 ? 1.0 : excl));
     if (ok) {
       al[i] = a;
       Tt[i] = T;
       const float w = fmul(a, T);
-      a_acc += (double)w;
+      F.acc += (double)w;
       wd += (double)w * (double)dmid[r * S1 + i];
     }
     Tc *= __shfl(incl, 63);
   }
-  a_acc = wave_sum_d(a_acc);
-  wd = wave_sum_d(wd);
-  const double A = (double)fadd((float)a_acc, 1e-10f);
-  const float gr0 = g_rgb ? g_rgb[r * 3 + 0] : 0.f, gr1 = g_rgb ? g_rgb[r * 3 + 1] : 0.f,
-              gr2 = g_rgb ? g_rgb[r * 3 + 2] : 0.f;
-  const double gd = g_depth ? (double)g_depth[r] : 0.0;
-  // white_bkgd: rgb += 1 - acc -> acc receives -sum(g_rgb)
-  const double ga = (g_acc ? (double)g_acc[r] : 0.0) - (white_bkgd ? (double)gr0 + gr1 + gr2 : 0.0);
+  F.acc = wave_sum(F.acc);
+  wd = wave_sum(wd);
+  const double A = (double)F.denom();
+  const CompositeGrads G(g_rgb, g_depth, g_acc, r, white_bkgd);
   __syncthreads();
   for (int i = l; i < S1; i += 64) {
     const int64_t q = r * S1 + i;
     const float w = fmul(al[i], Tt[i]);
-    double v = (double)gr0 * rad[q * 3 + 0] + (double)gr1 * rad[q * 3 + 1] + (double)gr2 * rad[q * 3 + 2] + ga;
-    v += gd * ((double)dmid[q] / A - wd / (A * A));
-    if (g_w) v += (double)g_w[q];
-    wb[i] = (float)v;
-    d_rad[q * 3 + 0] = fmul(w, gr0);
-    d_rad[q * 3 + 1] = fmul(w, gr1);
-    d_rad[q * 3 + 2] = fmul(w, gr2);
+    wb[i] = (float)G.weight_adjoint(rad + q * 3, (double)dmid[q], A, wd, g_w, q);
+    G.d_radiance(w, d_rad + q * 3);
   }
   __syncthreads();
   // alpha-bar from the reverse suffix sums (segments from the end, carried), then the quotient rule
@@ -539,10 +496,10 @@ __global__ __launch_bounds__(64) void neus_composite_bwd_kernel(const float* __r
     const int i = sg * 64 + l;
     const bool ok = i < S1;
     const double t = ok ? (double)wb[i] * al[i] * Tt[i] : 0.0;
-    const double incl = wave_incl_sum_rev(t, l);          // sum over lanes >= l of this segment
+    const double incl = wave_scan_add_rev(t);          // sum over lanes >= l of this segment
     const double suffix = carry + (incl - t);              // sum_{k > i}
     if (ok) {
-      const double u = (double)fadd(fsub(1.0f, al[i]), 1e-10f);
+      const double u = (double)transparency(al[i]);
       const double abar = (double)wb[i] * Tt[i] - suffix / u;
       const float num = fsub(c[i], c[i + 1]), den = fadd(c[i], 1e-10f);
       double ci_bar = 0.0, cn_bar = 0.0;
@@ -566,7 +523,7 @@ __global__ __launch_bounds__(64) void neus_composite_bwd_kernel(const float* __r
     d_sdf[r * S + k] = (float)(g * s);
     sbar += g * sd[k];
   }
-  sbar = wave_sum_d(sbar);
+  sbar = wave_sum(sbar);
   if (l == 0) d_s[r] = (float)sbar;
 }
 
@@ -576,25 +533,7 @@ __global__ __launch_bounds__(64) void neus_composite_bwd_kernel(const float* __r
 // passes no gradient to the network).  sigma = sdf_to_sigma(sdf, 1/beta, beta) (volsdf.py:16-35),
 // p_i = exp(-relu(sigma_i delta_i)), tau_i = (1 - p_i + 1e-10) prod_{j<i} p_j over the first S-1
 // samples; rgb = sum tau radiance[:S-1], depth = sum tau / (sum tau + 1e-10) d, acc = sum tau.  fp64
-// prefix products / sums rounded per element, as in the render kernel (volsdf_composite).
-__device__ __forceinline__ float vs_sigma_t(float v, float alpha, float beta) {
-  const float e = fmul(0.5f, expf(fdiv(-fabsf(v), beta)));
-  return fmul(alpha, v >= 0.0f ? e : fsub(1.0f, e));
-}
-__device__ __forceinline__ float vs_sdf_bg(const float* sdf, const float* pts, int64_t i, int use_bg, float r_bg,
-                                           bool& masked) {
-  float v = sdf[i];
-  masked = false;
-  if (use_bg) {
-    const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-    const float dbg = fsub(r_bg, norm3_ref(x, y, z));  // |x| as the render kernel (nr_volsdf.hip surface_sdf) and torch form it
-    if (dbg < v) {
-      v = dbg;
-      masked = true;
-    }
-  }
-  return v;
-}
+// prefix products / sums rounded per element (nr_composite.h).
 // With the NeRF++ background (volsdf.py:455-469) the N background samples follow the S inner ones:
 // sigma_bg [R,N] (the background net's raw sigma), radiance_bg [R,N,3], d_bg [R,N]; M = S + N samples
 // are integrated (p, tau over M-1, sigma over M).  N = 0: the inner samples only.
@@ -617,15 +556,15 @@ __global__ void volsdf_composite_fwd_kernel(const float* __restrict__ sdf, const
   const int M = S + bg.N, M1 = M - 1;
   auto dv = [&](int i) { return i < S ? d_all[r * S + i] : bg.d[r * bg.N + i - S]; };
   auto rv = [&](int i) { return i < S ? rad + (r * S + i) * 3 : bg.rad + (r * bg.N + i - S) * 3; };
-  double T = 1.0, a_acc = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
+  Composite A;
   bool m;
-  float sg = vs_sigma_t(vs_sdf_bg(sdf, pts, r * S, use_bg, r_bg, m), alpha, beta);
+  float sg = vs_sigma(vs_sdf_bg(sdf[r * S], pts + r * S * 3, use_bg, r_bg, m), alpha, beta);
   for (int i = 0; i < M; ++i) {
     float si;
     if (i < S) {
       const int64_t q = r * S + i;
-      const float v = vs_sdf_bg(sdf, pts, q, use_bg, r_bg, m);
-      si = vs_sigma_t(v, alpha, beta);
+      const float v = vs_sdf_bg(sdf[q], pts + q * 3, use_bg, r_bg, m);
+      si = vs_sigma(v, alpha, beta);
       if (sdf_out) sdf_out[q] = v;
     } else {
       si = bg.sig[r * bg.N + i - S];
@@ -633,33 +572,18 @@ __global__ void volsdf_composite_fwd_kernel(const float* __restrict__ sdf, const
     if (sigma_out) sigma_out[r * M + i] = si;
     if (i == 0) continue;
     // sample i-1's interval
-    const float p = expf(-fmaxf(fmul(sg, fsub(dv(i), dv(i - 1))), 0.0f));
-    const float tau = fmul(fadd(fsub(1.0f, p), 1e-10f), (float)T);
-    T *= (double)p;
+    const float p = vs_p(sg, fsub(dv(i), dv(i - 1)));
+    const float tau = A.weight_tau(p);
     const int64_t k = r * M1 + i - 1;
-    const float* rr = rv(i - 1);
-    c0 += (double)fmul(tau, rr[0]);
-    c1 += (double)fmul(tau, rr[1]);
-    c2 += (double)fmul(tau, rr[2]);
-    a_acc += (double)tau;
+    A.add(tau, rv(i - 1));
     tau_out[k] = tau;
     if (p_out) p_out[k] = p;
     sg = si;
   }
-  const float accf = (float)a_acc;
-  const float den = fadd(accf, 1e-10f);
+  const float den = A.denom();
   double dep = 0.0;
   for (int i = 0; i < M1; ++i) dep += (double)fmul(fdiv(tau_out[r * M1 + i], den), dv(i));
-  float o0 = (float)c0, o1 = (float)c1, o2 = (float)c2;
-  if (white_bkgd) {
-    const float bg_ = fsub(1.0f, accf);
-    o0 = fadd(o0, bg_); o1 = fadd(o1, bg_); o2 = fadd(o2, bg_);
-  }
-  rgb[r * 3 + 0] = o0;
-  rgb[r * 3 + 1] = o1;
-  rgb[r * 3 + 2] = o2;
-  depth[r] = (float)dep;
-  acc[r] = accf;
+  A.finish((float)dep, white_bkgd, r, rgb, depth, acc, nullptr);
 }
 
 // backward of the above: grads of rgb [R,3], depth [R], acc [R], tau [R,M-1] and the background-applied
@@ -694,17 +618,17 @@ __global__ void volsdf_composite_bwd_kernel(const float* __restrict__ sdf, const
   for (int i = 0; i < M; ++i) {
     bool m;
     if (i < S) {
-      v[i] = vs_sdf_bg(sdf, pts, r * S + i, use_bg, r_bg, m);
-      sg[i] = vs_sigma_t(v[i], alpha, beta);
+      v[i] = vs_sdf_bg(sdf[r * S + i], pts + (r * S + i) * 3, use_bg, r_bg, m);
+      sg[i] = vs_sigma(v[i], alpha, beta);
     } else {
       v[i] = 0.0f;
       sg[i] = bg.sig[r * bg.N + i - S];
     }
   }
   for (int i = 0; i < M1; ++i) {
-    p[i] = expf(-fmaxf(fmul(sg[i], fsub(dv(i + 1), dv(i))), 0.0f));
+    p[i] = vs_p(sg[i], fsub(dv(i + 1), dv(i)));
     P[i] = (float)T;
-    tau[i] = fmul(fadd(fsub(1.0f, p[i]), 1e-10f), P[i]);
+    tau[i] = vs_tau(p[i], P[i]);
     T *= (double)p[i];
     a_acc += (double)tau[i];
   }
@@ -728,7 +652,7 @@ __global__ void volsdf_composite_bwd_kernel(const float* __restrict__ sdf, const
       dr[0] = fmul(tau[i], gr0);
       dr[1] = fmul(tau[i], gr1);
       dr[2] = fmul(tau[i], gr2);
-      const double u = (double)fadd(fsub(1.0f, p[i]), 1e-10f);
+      const double u = (double)transparency(p[i]);
       const double pbar = (double)P[i] * (G - tb);
       G = tb * u + (double)p[i] * G;
       const float delta = fsub(dv(i + 1), dv(i));
@@ -751,7 +675,7 @@ __global__ void volsdf_composite_bwd_kernel(const float* __restrict__ sdf, const
       const int64_t q = r * S + i;
       vbar += g_sdf ? (double)g_sdf[q] : 0.0;  // NULL as a zero tensor, to the sign of a zero d_sdf
       bool m;
-      (void)vs_sdf_bg(sdf, pts, q, use_bg, r_bg, m);
+      (void)vs_sdf_bg(sdf[q], pts + q * 3, use_bg, r_bg, m);
       d_sdf[q] = m ? 0.0f : (float)vbar;
     } else {
       d_sig_bg[r * bg.N + i - S] = (float)sbar;
@@ -807,10 +731,6 @@ __global__ void volsdf_nerf_input_kernel(const float* __restrict__ ro, const flo
   for (int f = 0; f < 27; ++f) v_emb[i * 27 + f] = emb_f(f, vs, 4);
 }
 
-// F.softplus (beta 1, threshold 20) and its derivative (softplus_backward)
-__device__ __forceinline__ float sp1(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ double sp1_grad(float x) { return x > 20.0f ? 1.0 : 1.0 / (1.0 + exp(-(double)x)); }
-
 // composite with the background merged (neus.py:325-352): sample k < S-1 takes the SDF alpha and the
 // radiance net's colour where inside[k], else the background's; k >= S-1 are background samples.
 // alpha_out = 1 - exp(-softplus(sigma) dist), dist = d_{k+1} - d_k (1e10 for the last).
@@ -836,7 +756,7 @@ __global__ __launch_bounds__(64) void neus_composite_bg_fwd_kernel(
   float* lcol = lw + M;      // [3 M] colour
   float* ld = lcol + 3 * M;  // [M] depths
   for (int i = l; i < S; i += 64) {
-    const float v = sigmoidf_ref(fmul(sd[i], s));
+    const float v = neus_cdf(sd[i], s);
     c[i] = v;
     if (cdf_out) cdf_out[r * S + i] = v;
   }
@@ -846,11 +766,11 @@ __global__ __launch_bounds__(64) void neus_composite_bg_fwd_kernel(
     const float* col = rad_o + (r * M + k) * 3;
     float al;
     if (k < S1 && inside[r * S1 + k]) {
-      al = fmaxf(fdiv(fsub(c[k], c[k + 1]), fadd(c[k], 1e-10f)), 0.0f);
+      al = neus_alpha(c[k], c[k + 1]);
       col = rad + (r * S1 + k) * 3;
     } else {
-      const float dist = k + 1 < M ? fsub(dk[k + 1], d0) : 1e10f;
-      al = fsub(1.0f, expf(fmul(-sp1(sig_o[r * M + k]), dist)));
+      const float dist = nerfpp_dist(d0, dk, k + 1, k + 1 < M);
+      al = nerfpp_alpha(sig_o[r * M + k], dist);
     }
     la[k] = al;
     lcol[3 * k + 0] = col[0];
@@ -865,7 +785,7 @@ __global__ __launch_bounds__(64) void neus_composite_bg_fwd_kernel(
     for (int k = 0; k < M; ++k) {
       const float al = la[k];
       const float w = fmul(al, (float)T);
-      T *= (double)fadd(fsub(1.0f, al), 1e-10f);
+      T *= (double)transparency(al);
       c0 += (double)fmul(w, lcol[3 * k + 0]);
       c1 += (double)fmul(w, lcol[3 * k + 1]);
       c2 += (double)fmul(w, lcol[3 * k + 2]);
@@ -922,17 +842,17 @@ __global__ __launch_bounds__(64) void neus_composite_bg_bwd_kernel(
   for (int i = l; i < S; i += 64) {
     const float v = sd[i];
     ls[i] = v;
-    c[i] = sigmoidf_ref(fmul(v, s));
+    c[i] = neus_cdf(v, s);
   }
   __syncthreads();
   for (int k = l; k < M; k += 64) {
     const float d0 = dk[k];
     float a;
     if (is_in(k)) {
-      a = fmaxf(fdiv(fsub(c[k], c[k + 1]), fadd(c[k], 1e-10f)), 0.0f);
+      a = neus_alpha(c[k], c[k + 1]);
     } else {
-      const float dist = k + 1 < M ? fsub(dk[k + 1], d0) : 1e10f;
-      a = fsub(1.0f, expf(fmul(-sp1(sig_o[r * M + k]), dist)));
+      const float dist = nerfpp_dist(d0, dk, k + 1, k + 1 < M);
+      a = nerfpp_alpha(sig_o[r * M + k], dist);
     }
     al[k] = a;
     ld[k] = d0;
@@ -944,7 +864,7 @@ __global__ __launch_bounds__(64) void neus_composite_bg_bwd_kernel(
       const float a = al[k];
       Tt[k] = (float)T;
       w[k] = fmul(a, (float)T);
-      T *= (double)fadd(fsub(1.0f, a), 1e-10f);
+      T *= (double)transparency(a);
       a_acc += (double)w[k];
     }
     const float accf = (float)a_acc;
@@ -981,7 +901,7 @@ __global__ __launch_bounds__(64) void neus_composite_bg_bwd_kernel(
     double suffix = 0.0, sbar = 0.0;
     float cbar_next = 0.0f;  // gradient reaching c_{k+1} from alpha_{k+1}'s c_i term
     for (int k = M - 1; k >= 0; --k) {
-      const double u = (double)fadd(fsub(1.0f, al[k]), 1e-10f);
+      const double u = (double)transparency(al[k]);
       const double abar = (double)wb[k] * Tt[k] - suffix / u;
       suffix += (double)wb[k] * al[k] * Tt[k];
       lab[k] = abar;
@@ -1014,10 +934,10 @@ __global__ __launch_bounds__(64) void neus_composite_bg_bwd_kernel(
       d_sig[r * M + k] = 0.f;
     } else {
       // d alpha_out / d sigma = exp(-softplus(sigma) dist) dist softplus'(sigma)
-      const float dist = k + 1 < M ? fsub(ld[k + 1], ld[k]) : 1e10f;
+      const float dist = k + 1 < M ? fsub(ld[k + 1], ld[k]) : 1e10f;  // nerfpp_dist, in this kernel's load order
       const float x = sig_o[r * M + k];
-      const double e = exp(-(double)sp1(x) * (double)dist);
-      d_sig[r * M + k] = (float)(lab[k] * e * (double)dist * sp1_grad(x));
+      const double e = exp(-(double)softplus1(x) * (double)dist);
+      d_sig[r * M + k] = (float)(lab[k] * e * (double)dist * softplus1_grad(x));
     }
   }
   for (int i = l; i < S; i += 64) d_sdf[r * S + i] = lo[i];
@@ -1026,12 +946,7 @@ __global__ __launch_bounds__(64) void neus_composite_bg_bwd_kernel(
 // ---- UNISURF compositing with a graph (unisurf.py:219-236, get_opacity_from_surface :53-62) ------------
 // One thread per ray, P samples.  alpha_i = odds / (1 + odds), odds = exp(-logit_i); T_i = prod_{j<i}
 // (1 - alpha_j + 1e-10) (the cumprod of the shifted transparency); w_i = alpha_i T_i; rgb = sum w c,
-// acc = sum w, depth = sum w / (acc + 1e-10) d.  Same arithmetic as the render kernel (uni_composite):
-// fp64 prefix product and sums, rounded per element.
-__device__ __forceinline__ float uni_alpha(float lg) {
-  const float odds = expf(-lg);
-  return fdiv(odds, fadd(1.0f, odds));
-}
+// acc = sum w, depth = sum w / (acc + 1e-10) d.  fp64 prefix product and sums, rounded per element.
 __global__ void unisurf_composite_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ rad,
                                              const float* __restrict__ d_all, int64_t R, int P, int white_bkgd,
                                              float* __restrict__ rgb, float* __restrict__ depth,
@@ -1039,33 +954,19 @@ __global__ void unisurf_composite_fwd_kernel(const float* __restrict__ logits, c
                                              float* __restrict__ alpha_out) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
-  double T = 1.0, a_acc = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
+  Composite A;
   for (int i = 0; i < P; ++i) {
     const int64_t q = r * P + i;
     const float al = uni_alpha(logits[q]);
-    const float w = fmul(al, (float)T);
-    T *= (double)fadd(fsub(1.0f, al), 1e-10f);
-    c0 += (double)fmul(w, rad[q * 3 + 0]);
-    c1 += (double)fmul(w, rad[q * 3 + 1]);
-    c2 += (double)fmul(w, rad[q * 3 + 2]);
-    a_acc += (double)w;
+    const float w = A.weight(al);
+    A.add(w, rad + q * 3);
     w_out[q] = w;
     if (alpha_out) alpha_out[q] = al;
   }
-  const float accf = (float)a_acc;
-  const float den = fadd(accf, 1e-10f);
+  const float den = A.denom();
   double dep = 0.0;
   for (int i = 0; i < P; ++i) dep += (double)fmul(fdiv(w_out[r * P + i], den), d_all[r * P + i]);
-  float o0 = (float)c0, o1 = (float)c1, o2 = (float)c2;
-  if (white_bkgd) {
-    const float bg = fsub(1.0f, accf);
-    o0 = fadd(o0, bg); o1 = fadd(o1, bg); o2 = fadd(o2, bg);
-  }
-  rgb[r * 3 + 0] = o0;
-  rgb[r * 3 + 1] = o1;
-  rgb[r * 3 + 2] = o2;
-  depth[r] = (float)dep;
-  acc[r] = accf;
+  A.finish((float)dep, white_bkgd, r, rgb, depth, acc, nullptr);
 }
 
 // backward: G_i = dL/dw_i (rgb, acc, depth and direct weight gradients); w_i = alpha_i T_i with
@@ -1084,35 +985,28 @@ __global__ void unisurf_composite_bwd_kernel(const float* __restrict__ logits, c
   float* al = work + r * (3 * (int64_t)P);  // alpha, T, w
   float* Tt = al + P;
   float* w = Tt + P;
-  double T = 1.0, a_acc = 0.0, wd = 0.0;
+  Composite F;  // the forward again
+  double wd = 0.0;
   for (int i = 0; i < P; ++i) {
     const int64_t q = r * P + i;
     const float a = uni_alpha(logits[q]);
     al[i] = a;
-    Tt[i] = (float)T;
-    w[i] = fmul(a, (float)T);
-    T *= (double)fadd(fsub(1.0f, a), 1e-10f);
-    a_acc += (double)w[i];
+    Tt[i] = (float)F.T;
+    w[i] = F.weight(a);
+    F.acc += (double)w[i];
     wd += (double)w[i] * (double)d_all[q];
   }
-  const double A = (double)fadd((float)a_acc, 1e-10f);
-  const float gr0 = g_rgb ? g_rgb[r * 3 + 0] : 0.f, gr1 = g_rgb ? g_rgb[r * 3 + 1] : 0.f,
-              gr2 = g_rgb ? g_rgb[r * 3 + 2] : 0.f;
-  const double gd = g_depth ? (double)g_depth[r] : 0.0;
-  const double ga = (g_acc ? (double)g_acc[r] : 0.0) - (white_bkgd ? (double)gr0 + gr1 + gr2 : 0.0);
+  const double A = (double)F.denom();
+  const CompositeGrads g(g_rgb, g_depth, g_acc, r, white_bkgd);
   double S = 0.0;  // S_k for the current k (walking backwards)
   for (int k = P - 1; k >= 0; --k) {
     const int64_t q = r * P + k;
-    double G = (double)gr0 * rad[q * 3 + 0] + (double)gr1 * rad[q * 3 + 1] + (double)gr2 * rad[q * 3 + 2] + ga;
-    G += gd * ((double)d_all[q] / A - wd / (A * A));
-    if (g_w) G += (double)g_w[q];
+    const double G = g.weight_adjoint(rad + q * 3, (double)d_all[q], A, wd, g_w, q);
     const double abar = (double)Tt[k] * (G - S);
     const double a = al[k];
     d_logits[q] = (float)(-abar * a * (1.0 - a));
-    d_rad[q * 3 + 0] = fmul(w[k], gr0);
-    d_rad[q * 3 + 1] = fmul(w[k], gr1);
-    d_rad[q * 3 + 2] = fmul(w[k], gr2);
-    S = G * a + (double)fadd(fsub(1.0f, al[k]), 1e-10f) * S;  // S_{k-1}
+    g.d_radiance(w[k], d_rad + q * 3);
+    S = G * a + (double)transparency(al[k]) * S;  // S_{k-1}
   }
 }
 

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "nr_common.h"
+#include "nr_composite.h"
 #include "nr_mlp.h"
 #include "nr_neus.h"
 #include "nr_render.h"
@@ -16,10 +17,6 @@
 
 namespace nr {
 namespace {
-
-__device__ __forceinline__ float norm3f(float x, float y, float z) {
-  return norm3_ref(x, y, z);
-}
 
 // OPT-OUT (NR_UNISURF_ROOT_FUSABLE): the root finder (near / far, the march, the secant steps and their
 // points) keeps arithmetic that the compiler may fuse into FMAs, as it was built before fmul / fadd / fsub
@@ -50,10 +47,7 @@ __global__ void uni_prologue(UniChunk c, const float* __restrict__ rays_o, const
   if (r >= c.R) return;
   const float ox = rays_o[r * 3 + 0], oy = rays_o[r * 3 + 1], oz = rays_o[r * 3 + 2];
   float dx = rays_d[r * 3 + 0], dy = rays_d[r * 3 + 1], dz = rays_d[r * 3 + 2];
-  const float nn = fmaxf(norm3f(dx, dy, dz), 1e-12f);
-  dx = fdiv(dx, nn);
-  dy = fdiv(dy, nn);
-  dz = fdiv(dz, nn);
+  normalize3(dx, dy, dz);
   c.ro[r * 3 + 0] = ox; c.ro[r * 3 + 1] = oy; c.ro[r * 3 + 2] = oz;
   c.rd[r * 3 + 0] = dx; c.rd[r * 3 + 1] = dy; c.rd[r * 3 + 2] = dz;
   const float mid = -rf_add(rf_add(rf_mul(ox, dx), rf_mul(oy, dy)), rf_mul(oz, dz));
@@ -368,12 +362,12 @@ __global__ void uni_normalize(UniChunk c, int mode) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = (int64_t)c.R * c.P;
   if (p >= n) return;
-  const float x = c.nab_f[p * 3 + 0], y = c.nab_f[p * 3 + 1], z = c.nab_f[p * 3 + 2];
+  float x = c.nab_f[p * 3 + 0], y = c.nab_f[p * 3 + 1], z = c.nab_f[p * 3 + 2];
   if (mode == 0) {
-    const float d = fmaxf(norm3f(x, y, z), 1e-12f);
-    c.nrm_f[p * 3 + 0] = fdiv(x, d);
-    c.nrm_f[p * 3 + 1] = fdiv(y, d);
-    c.nrm_f[p * 3 + 2] = fdiv(z, d);
+    normalize3(x, y, z);
+    c.nrm_f[p * 3 + 0] = x;
+    c.nrm_f[p * 3 + 1] = y;
+    c.nrm_f[p * 3 + 2] = z;
   } else {
     const int64_t rf = p % c.R, s = p / c.R;
     const int64_t b = rf / c.nloc, rg = c.row_ray0 + rf % c.nloc;
@@ -395,8 +389,7 @@ __global__ void uni_composite(UniChunk c, UniOut o, int calc_normal, int white_b
   for (int i = 0; i < P; ++i) {
     const int64_t q = i * R + r;
     const float lg = c.sdf_f[q];
-    const float odds = expf(-lg);
-    const float alpha = fdiv(odds, fadd(1.0f, odds));
+    const float alpha = uni_alpha(lg);
     const float w = fmul(alpha, (float)T);
     T *= (double)fadd(fsub(1.0f, alpha), 1e-10f);
     a0 += (double)fmul(w, c.rad_f[q * 3 + 0]);
@@ -405,7 +398,7 @@ __global__ void uni_composite(UniChunk c, UniOut o, int calc_normal, int white_b
     a_acc += (double)w;
     const float nx = c.nab_f[q * 3 + 0], ny = c.nab_f[q * 3 + 1], nz = c.nab_f[q * 3 + 2];
     if (calc_normal) {
-      const float d = fmaxf(norm3f(nx, ny, nz), 1e-12f);
+      const float d = fmaxf(norm3_ref(nx, ny, nz), 1e-12f);
       n0 += (double)fmul(fdiv(nx, d), w);
       n1 += (double)fmul(fdiv(ny, d), w);
       n2 += (double)fmul(fdiv(nz, d), w);
@@ -418,11 +411,7 @@ __global__ void uni_composite(UniChunk c, UniOut o, int calc_normal, int white_b
       o.nablas[(rg * P + i) * 3 + 1] = ny;
       o.nablas[(rg * P + i) * 3 + 2] = nz;
     }
-    if (o.radiance) {
-      o.radiance[(rg * P + i) * 3 + 0] = c.rad_f[q * 3 + 0];
-      o.radiance[(rg * P + i) * 3 + 1] = c.rad_f[q * 3 + 1];
-      o.radiance[(rg * P + i) * 3 + 2] = c.rad_f[q * 3 + 2];
-    }
+    if (o.radiance) copy3(o.radiance + (rg * P + i) * 3, c.rad_f + q * 3);
   }
   const float accf = (float)a_acc;
   const float denom = fadd(accf, 1e-10f);
@@ -430,8 +419,7 @@ __global__ void uni_composite(UniChunk c, UniOut o, int calc_normal, int white_b
   T = 1.0;
   for (int i = 0; i < P; ++i) {  // second pass: weights normalised by their float sum
     const int64_t q = i * R + r;
-    const float odds = expf(-c.sdf_f[q]);
-    const float alpha = fdiv(odds, fadd(1.0f, odds));
+    const float alpha = uni_alpha(c.sdf_f[q]);
     const float w = fmul(alpha, (float)T);
     T *= (double)fadd(fsub(1.0f, alpha), 1e-10f);
     dep += (double)fmul(fdiv(w, denom), c.d_all[q]);

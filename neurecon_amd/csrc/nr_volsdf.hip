@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "nr_common.h"
+#include "nr_composite.h"
 #include "nr_mlp.h"
 #include "nr_render.h"
 #include "nr_volsdf.h"
@@ -31,25 +32,9 @@ __device__ __forceinline__ double wave_scan_add(double v) {
   return v;
 }
 
-__device__ __forceinline__ double wave_scan_mul(double v) {
-  const int l = threadIdx.x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double t = __shfl_up(v, o);
-    if (l >= o) v *= t;
-  }
-  return v;
-}
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
 
@@ -81,20 +66,10 @@ __device__ __forceinline__ int count_le(const float* __restrict__ u, int N, floa
   return g;
 }
 
-// sdf_to_sigma (volsdf.py:16-35): alpha * (sdf >= 0 ? 0.5 exp(-|sdf|/beta) : 1 - 0.5 exp(-|sdf|/beta))
-__device__ __forceinline__ float vs_sigma(float s, float alpha, float beta) {
-  const float e = fmul(0.5f, expf(fdiv(-fabsf(s), beta)));
-  return fmul(alpha, s >= 0.0f ? e : fsub(1.0f, e));
-}
-
 __device__ __forceinline__ void point_at(const VolChunk& c, int r, float d, float& x, float& y, float& z) {
   x = fadd(c.ro[r * 3 + 0], fmul(c.rd[r * 3 + 0], d));
   y = fadd(c.ro[r * 3 + 1], fmul(c.rd[r * 3 + 1], d));
   z = fadd(c.ro[r * 3 + 2], fmul(c.rd[r * 3 + 2], d));
-}
-
-__device__ __forceinline__ float norm3(float x, float y, float z) {
-  return norm3_ref(x, y, z);
 }
 
 // VolSDF.forward_surface (volsdf.py:310-315): min(sdf, r_bg - |x|) with the builtin background
@@ -102,7 +77,7 @@ __device__ __forceinline__ float surface_sdf(const VolChunk& c, int r, float d, 
   if (!c.use_bg) return s;
   float x, y, z;
   point_at(c, r, d, x, y, z);
-  return fminf(s, fsub(c.r_bg, norm3(x, y, z)));
+  return fminf(s, fsub(c.r_bg, norm3_ref(x, y, z)));
 }
 
 // One error-bound pass (volsdf.py:38-74) over the LDS list (D, S)[0..n): for every interval i the
@@ -366,10 +341,7 @@ __global__ __launch_bounds__(64) void volsdf_prologue(VolChunk c, const float* _
   const int r = blockIdx.x, l = threadIdx.x;
   const float ox = rays_o[r * 3 + 0], oy = rays_o[r * 3 + 1], oz = rays_o[r * 3 + 2];
   float dx = rays_d[r * 3 + 0], dy = rays_d[r * 3 + 1], dz = rays_d[r * 3 + 2];
-  const float nn = fmaxf(norm3(dx, dy, dz), 1e-12f);
-  dx = fdiv(dx, nn);
-  dy = fdiv(dy, nn);
-  dz = fdiv(dz, nn);
+  normalize3(dx, dy, dz);
   float far = c.far;
   if (c.N_out > 0) {
     // rend_util.get_sphere_intersection (rend_util.py:188-210), far end, clamp_min(0); rays that
@@ -515,27 +487,16 @@ __global__ __launch_bounds__(64) void volsdf_composite(VolChunk c, VolOut o, int
   // s.D: depths, s.S: sigma (inside: from the sdf; outside: the NeRF's raw sigma)
   for (int j = l; j < S; j += 64) {
     const float d = da[j];
-    float v = sf[j];
-    if (c.use_bg) {
-      const float dbg = fsub(c.r_bg, norm3(pp[j * 3], pp[j * 3 + 1], pp[j * 3 + 2]));
-      if (dbg < v) v = dbg;
-    }
+    bool masked;
+    const float v = vs_sdf_bg(sf[j], pp + j * 3, c.use_bg, c.r_bg, masked);
     const float sg = vs_sigma(v, c.alpha_net, c.beta_net);
     s.D[j] = d;
     s.S[j] = sg;
     if (o.sdf) o.sdf[ro * S + j] = v;
     if (o.d_vals) o.d_vals[ro * M + j] = d;
     if (o.sigma) o.sigma[ro * M + j] = sg;
-    if (o.nablas) {
-      o.nablas[(ro * S + j) * 3 + 0] = nb[j * 3 + 0];
-      o.nablas[(ro * S + j) * 3 + 1] = nb[j * 3 + 1];
-      o.nablas[(ro * S + j) * 3 + 2] = nb[j * 3 + 2];
-    }
-    if (o.radiance) {
-      o.radiance[(ro * M + j) * 3 + 0] = rad[j * 3 + 0];
-      o.radiance[(ro * M + j) * 3 + 1] = rad[j * 3 + 1];
-      o.radiance[(ro * M + j) * 3 + 2] = rad[j * 3 + 2];
-    }
+    if (o.nablas) copy3(o.nablas + (ro * S + j) * 3, nb + j * 3);
+    if (o.radiance) copy3(o.radiance + (ro * M + j) * 3, rad + j * 3);
   }
   for (int k = l; k < No; k += 64) {
     const int64_t i = (int64_t)r * No + k;
@@ -554,30 +515,24 @@ __global__ __launch_bounds__(64) void volsdf_composite(VolChunk c, VolOut o, int
   __syncthreads();
   // normals use the first min(#tau, #nablas) samples (volsdf.py:509-511)
   const int Nn = M - 1 < S ? M - 1 : S;
-  double T = 1.0, a_rgb0 = 0.0, a_rgb1 = 0.0, a_rgb2 = 0.0, a_acc = 0.0, a_n0 = 0.0, a_n1 = 0.0, a_n2 = 0.0;
+  Composite A;  // T: the carried product of the earlier segments; the sums: this lane's partials
   for (int base = 0; base < M - 1; base += 64) {
     const int i = base + l;
     const bool v = i < M - 1;
     float p = 1.0f;
-    if (v) p = expf(-fmaxf(fmul(s.S[i], fsub(s.D[i + 1], s.D[i])), 0.0f));
+    if (v) p = vs_p(s.S[i], fsub(s.D[i + 1], s.D[i]));
     const double inc = wave_scan_mul((double)p);
     double ex = __shfl_up(inc, 1);
     if (l == 0) ex = 1.0;
-    const float Ti = (float)(T * ex);
-    T *= __shfl(inc, 63);
+    const float Ti = (float)(A.T * ex);
+    A.T *= __shfl(inc, 63);
     if (v) {
-      const float tau = fmul(fadd(fsub(1.0f, p), 1e-10f), Ti);
-      const float* rr = i < S ? rad + i * 3 : rado + (i - S) * 3;
-      a_rgb0 += (double)fmul(tau, rr[0]);
-      a_rgb1 += (double)fmul(tau, rr[1]);
-      a_rgb2 += (double)fmul(tau, rr[2]);
-      a_acc += (double)tau;
+      const float tau = vs_tau(p, Ti);
+      A.add(tau, i < S ? rad + i * 3 : rado + (i - S) * 3);
       if (calc_normal && i < Nn) {
         float x = nb[i * 3 + 0], y = nb[i * 3 + 1], z = nb[i * 3 + 2];
-        const float nn = fmaxf(norm3(x, y, z), 1e-12f);
-        a_n0 += (double)fmul(fdiv(x, nn), tau);
-        a_n1 += (double)fmul(fdiv(y, nn), tau);
-        a_n2 += (double)fmul(fdiv(z, nn), tau);
+        normalize3(x, y, z);
+        A.add_normal(tau, x, y, z);
       }
       if (o.alpha) o.alpha[ro * (M - 1) + i] = fsub(1.0f, p);
       if (o.p_i) o.p_i[ro * (M - 1) + i] = p;
@@ -586,34 +541,19 @@ __global__ __launch_bounds__(64) void volsdf_composite(VolChunk c, VolOut o, int
     }
     __syncthreads();
   }
-  const float accf = (float)wave_sum(a_acc);
-  const float denom = fadd(accf, 1e-10f);
+  A.acc = wave_sum(A.acc);
+  const float denom = A.denom();
   double a_dep = 0.0;
   for (int i = l; i < M - 1; i += 64) a_dep += (double)fmul(fdiv(s.S[i], denom), s.D[i]);
   const float depth = (float)wave_sum(a_dep);
-  const float r0 = (float)wave_sum(a_rgb0), r1 = (float)wave_sum(a_rgb1), r2 = (float)wave_sum(a_rgb2);
-  float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+  A.c0 = wave_sum(A.c0), A.c1 = wave_sum(A.c1), A.c2 = wave_sum(A.c2);
   if (calc_normal) {
-    n0 = (float)wave_sum(a_n0);
-    n1 = (float)wave_sum(a_n1);
-    n2 = (float)wave_sum(a_n2);
+    A.n0 = wave_sum(A.n0);
+    A.n1 = wave_sum(A.n1);
+    A.n2 = wave_sum(A.n2);
   }
   if (l == 0) {
-    float q0 = r0, q1 = r1, q2 = r2;
-    if (white_bkgd) {
-      const float bg = fsub(1.0f, accf);
-      q0 = fadd(q0, bg); q1 = fadd(q1, bg); q2 = fadd(q2, bg);
-    }
-    o.rgb[ro * 3 + 0] = q0;
-    o.rgb[ro * 3 + 1] = q1;
-    o.rgb[ro * 3 + 2] = q2;
-    o.depth[ro] = depth;
-    o.acc[ro] = accf;
-    if (calc_normal && o.normals) {
-      o.normals[ro * 3 + 0] = n0;
-      o.normals[ro * 3 + 1] = n1;
-      o.normals[ro * 3 + 2] = n2;
-    }
+    A.finish(depth, white_bkgd, ro, o.rgb, o.depth, o.acc, calc_normal ? o.normals : nullptr);
     if (o.beta_map) o.beta_map[ro] = c.bmap[r];
     if (o.iter_usage) o.iter_usage[ro] = c.usage[r];
   }

@@ -1,12 +1,15 @@
 """Render fixed scenes with the three frameworks (render mode: every `extras` tensor; training: one
-forward + backward, the losses and every parameter's gradient) and save or compare them bit for bit:
+forward + backward, the losses and every parameter's gradient), run every case of tests/composite_cases.py
+through the training compositing kernels (forward and backward, every output and gradient) and save or
+compare all of it bit for bit:
 
     dump_render.py save PATH            writes them
     dump_render.py check PATH [PATH2]   compares this tree's with PATH's; exit status 1 on a difference
 
 With PATH2 (a second save of the same tree as PATH) the training tensors that differ between PATH and
 PATH2 are run-to-run noise of that tree (atomics in the weight gradients): they are listed and left
-out.  Render-mode tensors are never left out.  Used to A/B a change that must not alter any output bit."""
+out.  Render-mode and compositing-case tensors are never left out.  Used to A/B a change that must not
+alter any output bit."""
 import os
 import sys
 import types
@@ -45,6 +48,19 @@ def renders():
         for tag, kw in [('nerfpp', {}), ('nerfpp_detailed', dict(detailed_output=True))]:
             kw = dict(bench.render_kwargs(), N_outside=32, **kw)
             out['neus_' + tag] = _extras(neus.volume_render(ro[:, :1024], rd[:, :1024], mn, **kw))
+        # the compositing variants that only large sample counts reach (the dispatch at the end of neus_chunk,
+        # LDS bytes per ray against 65536), 8 rays, detailed.  N_samples = 64, the rest in N_importance; a round
+        # of the official upsampling takes at most 32 new samples, so N_upsample_iters is N_importance / 32
+        # rounded up to a divisor (the entries above use 4 rounds of 16):
+        #   neus_composite<1>            9 S 16 > 65536:        S = 512              (448 = 14 x 32)
+        #   neus_composite_outside_w<1>  (6 M + 4 S) 16 > 65536: S = 400, N_outside 32 (336 = 12 x 28)
+        #   neus_composite_outside       (6 M + 4 S) 4 > 65536:  S = 1600, N_outside 80 (1536 = 48 x 32)
+        for tag, m, S, iters, n_out in [('rpw1', model, 512, 14, 0), ('outside_rpw1', mn, 400, 12, 32),
+                                        ('outside_per_ray', mn, 1600, 48, 80)]:
+            kw = dict(bench.render_kwargs(), detailed_output=True, N_importance=S - 64, N_upsample_iters=iters,
+                      N_outside=n_out)
+            out['neus_' + tag] = _extras(neus.volume_render(ro[:, :8], rd[:, :8], m, **kw))
+            assert out['neus_' + tag]['cdf'].shape[-1] == S, (tag, out['neus_' + tag]['cdf'].shape)
 
         ro, rd = bench.camera_for(dev, 16, 32, 80.0, 2.7)
         vkw = dict(near=0.0, far=6.0, obj_bounding_radius=3.0, batched=True, calc_normal=True, detailed_output=True,
@@ -117,6 +133,15 @@ def train_steps():
     return out
 
 
+def composites():
+    """every case of tests/composite_cases.py through the training compositing kernels' C entry points,
+    forward and backward (the harness of tests/test_gpu_composite.py): all outputs and gradients"""
+    import composite_cases as CC
+    from test_gpu_composite import Harness
+    h = Harness()
+    return {'composite_' + c.name: {k: v.cpu() for k, v in h.run(c).items()} for c in CC.CASES}
+
+
 def _differing(a, b):
     assert sorted(a) == sorted(b), (sorted(a), sorted(b))
     bad = []
@@ -133,7 +158,7 @@ def _differing(a, b):
 
 def main():
     mode, path = sys.argv[1], sys.argv[2]
-    out = dict(renders(), **train_steps())
+    out = dict(renders(), **train_steps(), **composites())
     n = sum(len(v) for v in out.values())
     if mode == 'save':
         torch.save(out, path)
