@@ -47,6 +47,32 @@ def root_find(sdf_fn, o, d, near, far, N_steps=256, logit_tau=0.0, N_secant_step
     return dout, pt, hit, crossing
 
 
+def _strata(a, b, n, u=None):
+    """n depths on [a, b]: the points of linspace(n), or with uniforms u [..., n] one draw in each of the n
+    bins between the points of linspace(n + 1) (unisurf.py:158-169, :187-198)"""
+    t = torch.linspace(0.0, 1.0, steps=n if u is None else n + 1)
+    s = a.unsqueeze(-1) * (1 - t) + b.unsqueeze(-1) * t
+    if u is None:
+        return s
+    return s[..., :-1] + (s[..., 1:] - s[..., :-1]) * u
+
+
+def sample_depths(near, far, thr, dpred, crossing, interval, N_query=64, N_freespace=32, u_query=None, u_free=None):
+    """unisurf.py:152-203 from the root finder's depth (fill_inf=False) and crossing flag, all [..., N]:
+    the depth clamped to [near, far], and the sorted depths of N_query samples within `interval` of it plus
+    N_freespace samples between near and the interval's start (not below thr; the whole ray without a
+    crossing, or when that start is 0).  u_query / u_free: perturb=True with these uniforms."""
+    dpred = torch.max(torch.min(dpred, far), near)
+    d_up = torch.min(dpred + interval, far)
+    d_lo = torch.max(dpred - interval, near)
+    d_int = _strata(d_lo, d_up, N_query, u_query)
+    d_lo = torch.max(d_lo, thr)
+    d_lo = torch.where(crossing, d_lo, far)
+    d_lo = torch.where(d_lo < 1e-10, far, d_lo)
+    d_free = _strata(near, d_lo, N_freespace, u_free)
+    return dpred, torch.sort(torch.cat([d_free, d_int], -1), -1)[0]
+
+
 class UNISURFOracle:
     def __init__(self, sd, multires=6, use_view_dirs=True):
         self.sdf_net = SDFNet(sd, multires=multires)
@@ -60,25 +86,18 @@ class UNISURFOracle:
 
     def render(self, rays_o, rays_d, logit_tau=0.0, radius_of_interest=4.0, interval=1.0,
                too_close_threshold=0.1, N_query=64, N_freespace=32, netchunk=1048576, calc_normal=True,
-               white_bkgd=False, method='secant'):
+               white_bkgd=False, method='secant', near_bypass=None, far_bypass=None, u_query=None, u_free=None):
         o = rays_o.reshape(rays_o.shape[0], -1, 3).float()
         d = F.normalize(rays_d.reshape(rays_d.shape[0], -1, 3).float(), dim=-1)
-        B, N = o.shape[:2]
         near, far = R.near_far_from_sphere(o, d, r=radius_of_interest, keepdim=False)
+        if near_bypass is not None:                                           # unisurf.py:125-128
+            near = near_bypass * torch.ones_like(near)
+        if far_bypass is not None:
+            far = far_bypass * torch.ones_like(far)
         thr = near + (far - near) * too_close_threshold
         with torch.no_grad():
             dpred, pt, hit, crossing = root_find(self.sdf_net.sdf, o, d, near, far, logit_tau=logit_tau, method=method)
-        dpred = torch.max(torch.min(dpred, far), near)                        # unisurf.py:152-154
-        d_up = torch.min(dpred + interval, far)
-        d_lo = torch.max(dpred - interval, near)
-        t = torch.linspace(0.0, 1.0, steps=N_query)
-        d_int = d_lo.unsqueeze(-1) * (1 - t) + d_up.unsqueeze(-1) * t
-        d_lo = torch.max(d_lo, thr)                                           # unisurf.py:177-185
-        d_lo[crossing == 0] = far[crossing == 0]
-        d_lo[d_lo < 1e-10] = far[d_lo < 1e-10]
-        t = torch.linspace(0.0, 1.0, steps=N_freespace)
-        d_free = torch.ones([B, N, 1]) * near[..., None] * (1 - t) + d_lo.unsqueeze(-1) * t
-        d_all = torch.sort(torch.cat([d_free, d_int], -1), -1)[0]
+        dpred, d_all = sample_depths(near, far, thr, dpred, crossing, interval, N_query, N_freespace, u_query, u_free)
         out = self.integrate(o, d, d_all, netchunk=netchunk, calc_normal=calc_normal, white_bkgd=white_bkgd)
         out.update(surface_points=pt, mask_surface=hit, depth_surface=dpred)
         return out
